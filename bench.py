@@ -7,7 +7,18 @@ CompressorLZ4 frame-compress launch over the whole batch followed by one
 frame-decompress launch of the frames it produced (the kernels in
 kingdb_amd/csrc); inputs are resident in HBM before the timed region.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, checks every status word and
+length the timed steps wrote, writes its outputs where --dump-outputs is given,
+and prints the result line.  --full adds the legs beside the headline: the
+byte-for-byte check of the whole batch, the CPU baselines, the host-inclusive
+pipeline and the device copy rate of the roofline (each can still be switched
+off by its own --no-... option).  --dump-outputs DIR writes what the last timed
+step computed as DIR/<name>.npy (float32 / float64): the per-value lengths and
+status words, and the frames and decoded bytes of a fixed, seeded sample of the
+values (under 64 MB in all); the inputs are the same from run to run, so two
+builds can be compared output for output.
 
 For N > 1 the driver starts one process per GPU with torch.distributed.run;
 each rank owns its own shard of G1-long values (no collective on the data
@@ -71,7 +82,14 @@ def parse():
                    help="HBM traffic summary written by tools/pmc_traffic.py (default: "
                         "profiles/pmc_traffic.json, profiles/pmc_traffic_mixed.json for --workload mixed, "
                         "profiles/pmc_traffic_big.json for --workload big)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs beside the headline figure: the byte-for-byte check of the whole "
+                        "batch, the CPU baselines, the host-inclusive pipeline and the device copy rate")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step computed as DIR/<name>.npy")
     a = p.parse_args()
+    if not a.full:
+        a.no_cpu_baseline = a.no_host_inclusive = a.no_verify = True
     if a.values is None:
         a.values = 2560 if a.workload == "big" else 1 << 20
     if a.size is None:
@@ -287,6 +305,61 @@ def copy_bandwidth(batch, stream, reps: int = 5) -> float:
     return 2.0 * nb / (ms * 1e-3) / 1e9
 
 
+DUMP_PER_VALUE = 1 << 20     # per-value arrays are written whole up to this many values
+DUMP_SAMPLE_BYTES = 2 << 20  # raw bytes of the values whose frames and decoded bytes are written
+DUMP_SEED = 20
+
+
+def dump_sample(sizes: np.ndarray) -> tuple:
+    """The values a dump covers, the same for every run with the same sizes:
+    (indices of the per-value arrays, indices of the values whose bytes are
+    written), both ascending.  The byte sample is a seeded draw of whole values,
+    cut off where their raw bytes pass DUMP_SAMPLE_BYTES."""
+    n = len(sizes)
+    rng = np.random.default_rng(DUMP_SEED)
+    order = rng.permutation(n)
+    per_value = np.arange(n) if n <= DUMP_PER_VALUE else np.sort(order[:DUMP_PER_VALUE])
+    cum = np.cumsum(sizes[order[:DUMP_PER_VALUE]].astype(np.int64))
+    m = min(int(np.searchsorted(cum, DUMP_SAMPLE_BYTES)) + 1, len(cum))
+    return per_value, np.sort(order[:m])
+
+
+def gather_bytes(buf, off: np.ndarray, lens: np.ndarray, idx: np.ndarray, cap: int) -> np.ndarray:
+    """The bytes [off[i], off[i] + lens[i]) of a device buffer for i in idx, back
+    to back as float32; a piece is cut at `cap` bytes (a 1 MiB part's worth of
+    sample is its first `cap` bytes)."""
+    parts = [buf.download(min(int(lens[i]), cap), int(off[i])) for i in idx]
+    return np.concatenate(parts).astype(np.float32) if parts else np.zeros(0, np.float32)
+
+
+def write_dump(directory: str, arrays: dict) -> None:
+    os.makedirs(directory, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        # float32 holds every integer below 2^24 exactly; wider ones go out as float64
+        wide = a.dtype.kind in "iu" and a.size and int(a.max()) >= 1 << 24
+        a = a.astype(np.float64 if wide else np.float32)
+        total += a.nbytes
+        np.save(os.path.join(directory, name + ".npy"), a)
+    if total > 64_000_000:
+        raise SystemExit(f"bench: --dump-outputs wrote {total} B, over its 64 MB bound")
+
+
+def dump_batch(directory: str, batch, flen: np.ndarray, cst: np.ndarray, dst: np.ndarray) -> None:
+    """What compress() + decompress() of the last timed step left on the device:
+    frame lengths, decoded lengths and both status words per value, and the
+    frames and decoded bytes of the sampled values."""
+    per_value, idx = dump_sample(batch.sizes)
+    write_dump(directory, {
+        "frame_lens": flen[per_value], "compress_status": cst[per_value],
+        "decoded_lens": batch.out_lens()[per_value], "decompress_status": dst[per_value],
+        "sample_values": idx,
+        "sample_frames": gather_bytes(batch.frames, batch.frame_off, flen, idx, DUMP_SAMPLE_BYTES),
+        "sample_decoded": gather_bytes(batch.out, batch.src_off, batch.sizes, idx, DUMP_SAMPLE_BYTES),
+    })
+
+
 def ref_write_path(keys: np.ndarray, vals: np.ndarray) -> dict | None:
     """configs[4] CPU path: the reference's own Database::PutPart -> WriteBuffer ->
     HSTableManager (oracle/_ref/ref_db, built from /root/reference) on the same
@@ -428,6 +501,11 @@ def bench_get(args, world: int, rank: int, local: int, barrier, sync_all) -> Non
         ok = bool(np.array_equal(batch.src.download(t), batch.out.download(t)))
     if not ok:
         raise SystemExit("bench: read path output is not bit-exact -- refusing to report a number")
+    if args.dump_outputs and rank == 0:
+        per_value, idx = dump_sample(batch.sizes)
+        write_dump(args.dump_outputs, {
+            "out_lens": olen[per_value], "status": stat[per_value], "sample_values": idx,
+            "sample_decoded": gather_bytes(batch.out, batch.src_off, batch.sizes, idx, DUMP_SAMPLE_BYTES)})
     raw = float(batch.raw_bytes)
     frames = float(flen.sum())
     alg = raw + frames
@@ -508,6 +586,11 @@ def bench_put(args, world: int, rank: int, local: int, barrier, sync_all) -> Non
         pos += 25 + ks + (svc if svc else vs)
     if not ok:
         raise SystemExit("bench: write-path output malformed -- refusing to report a number")
+    if args.dump_outputs and rank == 0:
+        # the HSTable files of the last step: every file's size, and the head of the first file
+        write_dump(args.dump_outputs, {
+            "file_sizes": np.array([len(files[k]) for k in sorted(files)], np.int64),
+            "first_file_head": np.frombuffer(first[:2 * DUMP_SAMPLE_BYTES], np.uint8)})
     total = max_over_ranks(float(n), op="sum") * args.steps
     file_bytes = pp.writer.file_bytes()
     line = {
@@ -642,6 +725,8 @@ def main() -> None:
         ok = batch.roundtrip_ok()
     if not ok:
         raise SystemExit("bench: round trip is not bit-exact -- refusing to report a number")
+    if args.dump_outputs and rank == 0:
+        dump_batch(args.dump_outputs, batch, flen, cst, dst)
 
     raw = float(batch.raw_bytes)
     frames = float(flen.sum())
@@ -688,7 +773,7 @@ def main() -> None:
     total_raw = max_over_ranks(raw, op="sum") * args.steps
     value = total_raw / elapsed / GIB
     per_gpu = gather_ranks(raw * args.steps / mine / GIB)
-    copy_gbs = copy_bandwidth(batch, stream)
+    copy_gbs = copy_bandwidth(batch, stream) if args.full else None   # launches of its own
     line = {
         "metric": METRIC if args.workload != "big" else METRIC_BIG,
         "value": round(value, 3),
@@ -723,7 +808,8 @@ def main() -> None:
             "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_source,
             "traffic_refused": traffic_refused, "build_id": L.build_id(),
             "alg_bytes_per_launch": int(alg_bytes), "avg_launch_ms": round(dom_ms, 4),
-            "copy_gbs": round(copy_gbs, 1), "frac_of_copy": round(achieved / copy_gbs, 5),
+            "copy_gbs": round(copy_gbs, 1) if copy_gbs else None,
+            "frac_of_copy": round(achieved / copy_gbs, 5) if copy_gbs else None,
         },
         "per_gpu_gibs": [round(x, 3) for x in per_gpu],
         "kernels_ms": {"compress": round(c_ms, 4), "decompress": round(d_ms, 4)},

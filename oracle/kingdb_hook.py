@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """oracle/kingdb_hook.py -- TEST INFRASTRUCTURE: applies the write-buffer flush
 hook (kingdb_amd/kingdb_include/cache/lz4_flush.h) to a
-COPY of two reference sources outside the repository:
+COPY of two reference sources under the git-ignored oracle/_ref/:
 
   /root/reference/interface/database.cc  -> <out>/interface/database.cc
   /root/reference/cache/write_buffer.cc  -> <out>/cache/write_buffer.cc
 
-(out defaults to /tmp/kdb_hook_src).  Nothing of the reference is written into
-the repo; oracle/Makefile `kingdb_hook` compiles the copies into
+(out defaults to oracle/_ref/hook_src).  Nothing of the reference is committed
+to the repo; oracle/Makefile `kingdb_hook` compiles the copies into
 oracle/_ref/kingdb_hook/ beside the untouched rest of the tree.
 
 The edits, each anchored on text that must occur exactly once:
@@ -230,4 +230,4 @@ def apply(out: str) -> None:
 
 
 if __name__ == "__main__":
-    apply(sys.argv[1] if len(sys.argv) > 1 else "/tmp/kdb_hook_src")
+    apply(sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.abspath(__file__)), "_ref", "hook_src"))

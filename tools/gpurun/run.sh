@@ -66,13 +66,13 @@ for s in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "${O}_smoke.log" 2>&1 || fail smoke $? "${O}_smoke.log"
       cat "${O}_smoke.log" ;;
     bench)
-      timeout -k 10 600 python bench.py --host-inclusive > "${O}_bench.json" 2> "${O}_bench.err" || fail bench $? "${O}_bench.err"
+      timeout -k 10 600 python bench.py --full --host-inclusive >"${O}_bench.json" 2> "${O}_bench.err" || fail bench $? "${O}_bench.err"
       cat "${O}_bench.json" ;;
     quick)
       timeout -k 10 300 python bench.py --no-cpu-baseline --no-host-inclusive > "${O}_quick.json" 2> "${O}_quick.err" || fail quick $? "${O}_quick.err"
       line "${O}_quick.json" ;;
     mixed|put|get|big)
-      timeout -k 10 500 python bench.py --workload $s > "${O}_$s.json" 2> "${O}_$s.err" || fail $s $? "${O}_$s.err"
+      timeout -k 10 500 python bench.py --full --workload $s >"${O}_$s.json" 2> "${O}_$s.err" || fail $s $? "${O}_$s.err"
       cat "${O}_$s.json" ;;
     prof) prof bench --no-cpu-baseline --no-host-inclusive --steps 5 --warmup 1 ;;
     profmixed) prof mixed --workload mixed --no-cpu-baseline --steps 3 --warmup 1 ;;
