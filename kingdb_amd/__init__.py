@@ -26,8 +26,10 @@ from .lz4 import (  # noqa: F401
     set_device,
 )
 
+from .index import HSTableIndex  # noqa: F401,E402
+
 __all__ = [
-    "DeviceBatch", "DeviceBuffer", "Event", "Stream", "build_id", "compress_blocks", "compress_bound",
+    "HSTableIndex", "DeviceBatch", "DeviceBuffer", "Event", "Stream", "build_id", "compress_blocks", "compress_bound",
     "compress_frames", "compress_limited_output", "decompress_blocks", "decompress_frames",
     "decompress_safe_partial", "device_count", "frame_bound", "get_device", "last_kernels", "selftest",
     "set_device",

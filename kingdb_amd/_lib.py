@@ -79,6 +79,13 @@ SIGNATURES = {
     "kdb_get_scratch_bytes": (_u64, [_u32, _u64]),
     "kdb_get_values_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _i, _vp, _vp, _u64, _u32, _u32, _vp,
                                   _u64, _vp, _vp]),
+    "kdb_index_create": (_i, [_u32, _c.POINTER(_vp)]),
+    "kdb_index_destroy": (_i, [_vp]),
+    "kdb_index_load_files": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _c.POINTER(_u64)]),
+    "kdb_index_entry_count": (_i, [_vp, _c.POINTER(_u64)]),
+    "kdb_index_pairs": (_i, [_vp, _vp, _vp]),
+    "kdb_index_get_scratch_bytes": (_u64, [_u32]),
+    "kdb_index_get_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _i, _u64, _vp, _u64] + [_vp] * 10),
     "kdb_hstable_db_options": (_i, [_u64, _u32, _vp]),
     "kdb_hstable_writer_create": (_i, [_u64, _u32, _c.POINTER(_vp)]),
     "kdb_hstable_writer_create2": (_i, [_u64, _u32, _u32, _c.POINTER(_vp)]),

@@ -1,0 +1,722 @@
+// kingdb_amd/csrc/index.hip -- Get by key on the GPU: the index over a set of
+// closed HSTable files and the batched lookup that feeds kdb_get_values_batch.
+//
+// Reference semantics:
+//   * HSTableManager::LoadDatabase / LoadFile (storage/hstable_manager.h:906-1099):
+//     files in (timestamp, fileid) order, each file's offset array inserted row
+//     by row into a multimap<hashed key, fileid << 32 | offset>;
+//   * StorageEngine::GetWithIndex / GetEntry (storage/storage_engine.h:424-521):
+//     the candidates of the key's hash, newest first; EntryHeader::DecodeFrom,
+//     the validity checks, the key compare;
+//   * Database::GetRaw (interface/database.cc:9-75): a delete entry is
+//     NotFound, MultipartRequired for large compressed values.
+//
+// Load (synchronous, like Database::Open):
+//   index_file_kernel    workgroup per file: HSTableHeader, footer, magic,
+//                        bounds, CRC32C of the offset array (wave CRC, the
+//                        waves' parts combined with the GF(2) shift)
+//   host                 files ordered by (timestamp, fileid); the exclusive
+//                        sum of num_entries numbers every row (its insertion
+//                        order into the reference's multimap)
+//   index_count_kernel   terminator bytes (top bit clear) per 256-byte tile
+//   scan                 launch_exclusive_scan over the tiles
+//   index_parse_kernel   thread per byte: a terminator's rank is its varint's
+//                        number; varints 2r and 2r+1 are row r; the owner walks
+//                        back to the varint's first byte (across wave and
+//                        workgroup boundaries: plain global reads inside the
+//                        row region) and assembles the value
+//   index_hist_kernel / scan / index_fill_kernel
+//                        CSR buckets over hash & (B - 1), B a power of two >= 2 x rows
+// Lookup (stream-ordered):
+//   index_get_kernel     wave per key: hash, bucket scan, candidates in
+//                        descending sequence number, header decode + checks
+//                        (hstable_decode.h), key compare and crc32c(key) on the lanes
+//   scan                 64-byte-aligned output slots
+//   index_summary_kernel what the host needs to size the decode
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <new>
+#include <vector>
+
+#include "../../include/kdb_lz4.h"
+#include "../../include/kdb_put.h"
+#include "crc_device.h"
+#include "hash_device.h"
+#include "hstable_decode.h"
+#include "lz4_device.h"
+
+namespace hs = kdb_hstable;
+
+namespace kdb_lz4 {
+
+hipError_t launch_exclusive_scan(hipStream_t st, const uint32_t* len, uint32_t n, uint64_t* off, uint64_t* total);
+
+namespace {
+
+constexpr int kFileBlock = 1024;           // index_file_kernel: 16 waves share one file's CRC
+constexpr uint32_t kParseTile = 256;       // bytes of an offset array per workgroup, one per thread
+constexpr int kGetBlock = 256;
+constexpr uint32_t kKeyStage = 256;        // query keys up to this many bytes are hashed from LDS
+constexpr uint32_t kHeaderStage = 64;      // >= hs::kMaxEntryHeader, one byte per lane
+static_assert(kHeaderStage >= hs::kMaxEntryHeader && kHeaderStage <= 64, "one load per lane covers a header");
+constexpr uint64_t kMaxFileSize = 0xFFFFFF00ull;   // entry offsets are 32-bit (OffsetArrayRow)
+constexpr uint64_t kMaxRows = 1ull << 30;
+
+struct FileRec {
+  uint64_t num_entries, offset_indexes, timestamp;
+  uint32_t flags;
+  int32_t status;
+};
+
+struct ParseFile {
+  uint64_t reg_off;      // the row region [offset_indexes, size - 36), in the files buffer
+  uint64_t reg_len;
+  uint64_t nvar;         // 2 * num_entries: the varints that count
+  uint64_t row_base;     // sequence number of the file's row 0
+  uint32_t first_tile, ntiles;
+  uint32_t slot;         // the file's position in the caller's arrays
+  uint32_t pad;
+};
+
+struct Slot {
+  uint64_t hash;
+  uint32_t file;         // file slot
+  uint32_t offset;       // entry offset in the file
+  uint32_t seq;          // insertion order into the reference's multimap
+  uint32_t pad;
+};
+
+struct BytesMsg {
+  const uint8_t* p;
+  __device__ uint32_t feed(uint64_t a, uint64_t b, uint32_t c, const uint32_t* s_t) const {
+    for (uint64_t m = a; m < b; m++) c = crc::step(c, p[m], s_t);
+    return c;
+  }
+};
+
+__global__ __launch_bounds__(kFileBlock) void index_file_kernel(const uint8_t* __restrict__ files,
+                                                                const uint64_t* __restrict__ file_off,
+                                                                const uint64_t* __restrict__ file_size,
+                                                                FileRec* __restrict__ rec) {
+  constexpr uint32_t kWaves = kFileBlock / 64;
+  __shared__ uint32_t s_t[256];
+  __shared__ uint32_t s_crc[kWaves];
+  __shared__ FileRec s_rec;
+  __shared__ uint32_t s_want;
+  crc::stage_table(s_t);
+  __syncthreads();
+  const uint32_t f = blockIdx.x;
+  const uint8_t* p = files + file_off[f];
+  const uint64_t size = file_size[f];
+  if (threadIdx.x == 0) {
+    FileRec r{0, 0, 0, 0, 0};
+    hs::FileHeader fh;
+    hs::Footer ft;
+    uint32_t want = 0;
+    if (size <= hs::kHeaderBlock || !hs::decode_file_header(p, size, &fh)) {
+      r.status = -2;
+    } else {
+      uint32_t c = 0xFFFFFFFFu;                      // crc32c::Value(buffer + 4, 20), format.h:407
+      for (uint32_t i = 4; i < 24; i++) c = crc::step(c, p[i], s_t);
+      if ((c ^ 0xFFFFFFFFu) != fh.crc32) {
+        r.status = -2;
+      } else if (!hs::decode_footer(p, size, &ft)) {
+        r.status = -1;
+      } else {
+        r.num_entries = ft.num_entries;
+        r.offset_indexes = ft.offset_indexes;
+        r.timestamp = fh.timestamp;
+        r.flags = ft.flags;
+        want = ft.crc32;
+      }
+    }
+    s_rec = r;
+    s_want = want;
+  }
+  __syncthreads();
+  if (s_rec.status != 0) {
+    if (threadIdx.x == 0) rec[f] = s_rec;
+    return;
+  }
+  // CRC32C over [offset_indexes, size - 4) (LoadFile:1068): a contiguous part per wave
+  const uint64_t oi = s_rec.offset_indexes;
+  const uint64_t n = size - 4u - oi;                 // oi <= size - 36
+  const uint64_t part = (n + kWaves - 1u) / kWaves;
+  const uint32_t w = threadIdx.x / 64u;
+  {
+    const uint64_t a = min((uint64_t)w * part, n), b = min(a + part, n);
+    const BytesMsg msg{p + oi + a};
+    const uint32_t c = crc::extend_wave(0u, b - a, msg, s_t);
+    if (lane_id() == 0) s_crc[w] = c;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t c = s_crc[0];                           // crc(A || B) = crc(B) ^ shift(crc(A), |B|)
+    for (uint32_t k = 1; k < kWaves; k++) {
+      const uint64_t a = min((uint64_t)k * part, n), b = min(a + part, n);
+      c = s_crc[k] ^ crc::shift_n(c, b - a);
+    }
+    FileRec r = s_rec;
+    const uint64_t rows_bytes = size - hs::kFooterSize - oi;
+    if (c != s_want) r.status = -1;
+    else if (r.num_entries > rows_bytes / 2u) r.status = -3;   // a row is at least two bytes
+    rec[f] = r;
+  }
+}
+
+// Terminators of the tile and, per thread, whether its byte is one.
+__device__ __forceinline__ bool tile_byte(const uint8_t* __restrict__ files, const ParseFile& F, uint32_t t,
+                                          uint64_t* pos_out) {
+  const uint64_t pos = (uint64_t)(t - F.first_tile) * kParseTile + threadIdx.x;
+  *pos_out = pos;
+  return pos < F.reg_len && (files[F.reg_off + pos] & 0x80u) == 0;
+}
+
+__global__ __launch_bounds__(kParseTile) void index_count_kernel(const uint8_t* __restrict__ files,
+                                                                 const ParseFile* __restrict__ pf,
+                                                                 const uint32_t* __restrict__ tile_file,
+                                                                 uint32_t* __restrict__ tile_count) {
+  __shared__ uint32_t s_w[kParseTile / 64];
+  const uint32_t t = blockIdx.x;
+  const ParseFile F = pf[tile_file[t]];
+  uint64_t pos;
+  const bool term = tile_byte(files, F, t, &pos);
+  const uint64_t m = ballot(term);
+  if (lane_id() == 0) s_w[threadIdx.x / 64u] = (uint32_t)__popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t s = 0;
+    for (uint32_t k = 0; k < kParseTile / 64; k++) s += s_w[k];
+    tile_count[t] = s;
+  }
+}
+
+__global__ __launch_bounds__(kParseTile) void index_parse_kernel(
+    const uint8_t* __restrict__ files, const ParseFile* __restrict__ pf, const uint32_t* __restrict__ tile_file,
+    const uint64_t* __restrict__ tile_prefix, uint64_t* __restrict__ row_hash, uint32_t* __restrict__ row_off,
+    uint32_t* __restrict__ row_file, uint32_t* __restrict__ malformed) {
+  __shared__ uint32_t s_w[kParseTile / 64];
+  const uint32_t t = blockIdx.x;
+  const ParseFile F = pf[tile_file[t]];
+  uint64_t pos;
+  const bool term = tile_byte(files, F, t, &pos);
+  const uint64_t m = ballot(term);
+  const uint32_t w = threadIdx.x / 64u;
+  if (lane_id() == 0) s_w[w] = (uint32_t)__popcll(m);
+  __syncthreads();
+  uint64_t k = tile_prefix[t] - tile_prefix[F.first_tile];   // varints of the file before this tile
+  uint32_t tile_total = 0;
+  for (uint32_t i = 0; i < kParseTile / 64; i++) {
+    if (i < w) k += s_w[i];
+    tile_total += s_w[i];
+  }
+  if (threadIdx.x == 0 && t == F.first_tile + F.ntiles - 1u &&
+      tile_prefix[t] - tile_prefix[F.first_tile] + tile_total < F.nvar)
+    malformed[F.slot] = 1u;                                  // fewer varints than 2 * num_entries
+  if (!term) return;
+  k += (uint64_t)__popcll(m & mask_lt(lane_id()));
+  if (k >= F.nvar) return;                                    // only the first 2 * num_entries count
+  const uint8_t* reg = files + F.reg_off;
+  uint64_t start = pos;
+  uint32_t len = 1;
+  while (start > 0 && len <= 10u && (reg[start - 1u] & 0x80u)) {
+    start--;
+    len++;
+  }
+  const bool is_offset = (k & 1u) != 0;
+  if (len > (is_offset ? 5u : 10u)) {                         // coding.cc:147, 175
+    malformed[F.slot] = 1u;
+    return;
+  }
+  uint64_t v = 0;
+  for (uint32_t i = 0; i < len; i++) v |= (uint64_t)(reg[start + i] & 127u) << (7u * i);
+  const uint64_t r = F.row_base + (k >> 1);
+  if (is_offset) {
+    row_off[r] = (uint32_t)v;
+  } else {
+    row_hash[r] = v;
+    row_file[r] = F.slot;
+  }
+}
+
+__global__ void index_hist_kernel(const uint64_t* __restrict__ row_hash, uint32_t n, uint64_t mask,
+                                  uint32_t* __restrict__ count) {
+  for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x)
+    atomicAdd(&count[row_hash[r] & mask], 1u);
+}
+
+// count[b] still holds the bucket's size: each row takes the next free slot from the back.
+__global__ void index_fill_kernel(const uint64_t* __restrict__ row_hash, const uint32_t* __restrict__ row_off,
+                                  const uint32_t* __restrict__ row_file, uint32_t n, uint64_t mask,
+                                  const uint64_t* __restrict__ start, uint32_t* __restrict__ count,
+                                  Slot* __restrict__ slots) {
+  for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x) {
+    const uint64_t h = row_hash[r];
+    const uint64_t b = h & mask;
+    const uint32_t at = atomicSub(&count[b], 1u) - 1u;
+    slots[start[b] + at] = Slot{h, row_file[r], row_off[r], r, 0u};
+  }
+}
+
+struct IndexView {
+  const uint8_t* files;
+  const uint64_t* file_off;
+  const uint64_t* file_size;
+  const uint32_t* fileid;
+  const uint64_t* start;     // nbuckets + 1
+  const Slot* slots;
+  uint64_t mask;             // nbuckets - 1
+  uint32_t nrows;
+  uint32_t hash_type;
+};
+
+typedef uint32_t __attribute__((aligned(1))) u32u;
+
+// LDS bytes written by some lanes of the wave are read by others after this.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ uint64_t wave_max64(uint64_t x) {
+#pragma unroll
+  for (int s = 1; s < 64; s <<= 1) {
+    const uint64_t o = __shfl_xor((unsigned long long)x, s);
+    x = o > x ? o : x;
+  }
+  return x;
+}
+__device__ __forceinline__ uint64_t wave_sum64(uint64_t x) {
+#pragma unroll
+  for (int s = 1; s < 64; s <<= 1) x += __shfl_xor((unsigned long long)x, s);
+  return x;
+}
+
+// Wave per key.  Everything but the bucket scan, the key compare and the
+// key's CRC is the same on every lane (same addresses: broadcast loads).
+__global__ __launch_bounds__(kGetBlock) void index_get_kernel(
+    IndexView ix, const uint8_t* __restrict__ keys, const uint64_t* __restrict__ key_off,
+    const uint32_t* __restrict__ key_len, uint32_t n, int verify_header, uint64_t multipart_required,
+    uint64_t* __restrict__ stored_off, uint64_t* __restrict__ avail, uint64_t* __restrict__ svc,
+    uint64_t* __restrict__ size, uint32_t* __restrict__ checksum, uint32_t* __restrict__ checksum_initial,
+    uint32_t* __restrict__ slot_len, uint64_t* __restrict__ location, int32_t* __restrict__ status) {
+  __shared__ uint32_t s_t[256];
+  // Per wave: the query key (when it fits) and the candidate's first bytes,
+  // fetched by the lanes in one load each.  The hash and the header decode
+  // walk bytes one after the other; from global memory every step of those
+  // chains is a load of its own (3.65 -> 3.53 ms per 1 Mi lookups of 16-byte
+  // keys).
+  __shared__ uint8_t s_key[kGetBlock / 64][kKeyStage];
+  __shared__ uint8_t s_hdr[kGetBlock / 64][kHeaderStage];
+  crc::stage_table(s_t);
+  __syncthreads();
+  const uint32_t lane = lane_id();
+  const uint32_t wib = threadIdx.x / 64u;
+  const uint32_t nw = gridDim.x * (kGetBlock / 64);
+  for (uint32_t v = blockIdx.x * (kGetBlock / 64) + wib; v < n; v += nw) {
+    const uint32_t klen = uni(key_len[v]);
+    const uint8_t* key = keys + key_off[v];
+    if (klen <= kKeyStage) {
+      for (uint32_t i = lane; i < klen; i += 64u) s_key[wib][i] = key[i];
+      wave_lds_sync();
+      key = s_key[wib];
+    }
+    const uint64_t h = ix.hash_type == 1 ? xxh64(key, klen) : murmur3_64(key, klen);
+    int32_t st = KDB_GET_NOTFOUND;
+    uint64_t o_stored = 0, o_avail = 0, o_svc = 0, o_size = 0, o_loc = 0;
+    uint32_t o_ck = 0, o_ci = 0;
+    if (ix.nrows) {
+      const uint64_t b = h & ix.mask;
+      const uint64_t s0 = ix.start[b], s1 = ix.start[b + 1u];
+      uint64_t bound = ~0ull;               // candidates taken so far have (seq + 1) << 32 | slot >= bound
+      for (;;) {
+        uint64_t best = 0;
+        for (uint64_t i = s0 + lane; i < s1; i += 64u) {
+          const Slot s = ix.slots[i];
+          const uint64_t pk = ((uint64_t)s.seq + 1u) << 32 | (uint32_t)(i - s0);
+          if (s.hash == h && pk < bound && pk > best) best = pk;
+        }
+        best = wave_max64(best);
+        if (best == 0) break;
+        bound = best;
+        const Slot c = ix.slots[s0 + (uint32_t)best];
+        const uint64_t fo = ix.file_off[c.file], fs = ix.file_size[c.file];
+        const uint8_t* file = ix.files + fo;
+        hs::EntryHeader hd;
+        // locate_entry() on a copy of the candidate's first bytes: a header is
+        // at most kMaxEntryHeader <= kHeaderStage bytes, so decoding
+        // min(room, kHeaderStage) bytes is decoding all `room` of them.
+        // A candidate that does not decode or validate is skipped (GetWithIndex:446).
+        const uint64_t room = c.offset < fs ? min(fs - c.offset, (uint64_t)kHeaderStage) : 0u;
+        wave_lds_sync();
+        if (lane < room) s_hdr[wib][lane] = file[(uint64_t)c.offset + lane];
+        wave_lds_sync();
+        if (room == 0 || hs::decode_entry_header(s_hdr[wib], room, verify_header != 0, &hd) != hs::kDecodeOk ||
+            !hs::entry_valid(hd, c.offset, fs))
+          continue;
+        if (hd.size_key != klen) continue;
+        // locate_entry: [offset + size_header, + size_key) lies inside the file
+        const uint8_t* stored_key = file + c.offset + hd.size_header;
+        bool diff = false;
+        for (uint32_t o = 4u * lane; o < klen; o += 256u) {
+          if (o + 4u <= klen) {
+            diff |= *reinterpret_cast<const u32u*>(stored_key + o) != *reinterpret_cast<const u32u*>(key + o);
+          } else {
+            for (uint32_t j = o; j < klen; j++) diff |= stored_key[j] != key[j];
+          }
+        }
+        if (ballot(diff) != 0) continue;
+        o_loc = (uint64_t)ix.fileid[c.file] << 32 | c.offset;
+        if (hd.flags & hs::kTypeDelete) {                       // database.cc:16, storage_engine.h:511
+          st = KDB_GET_DELETED;
+        } else if (hs::is_compressed(hd) && hd.size_value > multipart_required) {   // database.cc:60-63
+          st = KDB_GET_MULTIPART;
+        } else {
+          st = 0;
+          uint64_t svo = 0;
+          hs::size_value_offset(hd, &svo);
+          o_stored = fo + c.offset + hd.size_header + klen;
+          o_avail = svo;
+          o_svc = hd.size_value_compressed;
+          o_size = hd.size_value;
+          o_ck = hd.checksum_content;
+          const BytesMsg msg{key};                               // == the stored key
+          o_ci = crc::extend_wave(0u, klen, msg, s_t);          // storage_engine.h:497-500
+        }
+        break;
+      }
+    }
+    if (lane == 0) {
+      stored_off[v] = o_stored;
+      avail[v] = o_avail;
+      svc[v] = o_svc;
+      size[v] = o_size;
+      checksum[v] = o_ck;
+      checksum_initial[v] = o_ci;
+      slot_len[v] = (uint32_t)((o_size + 63u) & ~63ull);
+      location[v] = o_loc;
+      status[v] = st;
+    }
+  }
+}
+
+// summary: [0] rows found, [1] output bytes (the scan's total), [2] max avail,
+// [3] max size, [4] sum of avail / 8 + 1.  One atomic per wave and field.
+__global__ __launch_bounds__(256) void index_summary_kernel(const uint64_t* __restrict__ avail,
+                                                            const uint64_t* __restrict__ size,
+                                                            const int32_t* __restrict__ status, uint32_t n,
+                                                            unsigned long long* __restrict__ summary) {
+  uint64_t found = 0, max_avail = 0, max_size = 0, frames = 0;
+  for (uint32_t v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x) {
+    found += status[v] == 0;
+    const uint64_t a = avail[v], s = size[v];
+    max_avail = a > max_avail ? a : max_avail;
+    max_size = s > max_size ? s : max_size;
+    frames += a / 8u + 1u;
+  }
+  found = wave_sum64(found);
+  frames = wave_sum64(frames);
+  max_avail = wave_max64(max_avail);
+  max_size = wave_max64(max_size);
+  if (lane_id() == 0) {
+    atomicAdd(&summary[0], (unsigned long long)found);
+    atomicMax(&summary[2], (unsigned long long)max_avail);
+    atomicMax(&summary[3], (unsigned long long)max_size);
+    atomicAdd(&summary[4], (unsigned long long)frames);
+  }
+}
+
+}  // namespace
+}  // namespace kdb_lz4
+
+using namespace kdb_lz4;
+
+struct kdb_index {
+  uint32_t hash_type = 1;
+  const uint8_t* d_files = nullptr;      // the caller's
+  uint32_t nfiles = 0;
+  uint64_t nrows = 0, nbuckets = 0;
+  uint64_t* d_file_off = nullptr;
+  uint64_t* d_file_size = nullptr;
+  uint32_t* d_fileid = nullptr;
+  uint64_t* d_start = nullptr;
+  Slot* d_slots = nullptr;
+  uint64_t* d_row_hash = nullptr;
+  uint32_t* d_row_off = nullptr;
+  uint32_t* d_row_file = nullptr;
+  std::vector<uint32_t> fileid;
+};
+
+namespace {
+
+template <class T>
+void dfree(T*& p) {
+  if (p) (void)hipFree(p);
+  p = nullptr;
+}
+
+void index_release(kdb_index* ix) {
+  dfree(ix->d_file_off);
+  dfree(ix->d_file_size);
+  dfree(ix->d_fileid);
+  dfree(ix->d_start);
+  dfree(ix->d_slots);
+  dfree(ix->d_row_hash);
+  dfree(ix->d_row_off);
+  dfree(ix->d_row_file);
+  ix->d_files = nullptr;
+  ix->nfiles = 0;
+  ix->nrows = ix->nbuckets = 0;
+  ix->fileid.clear();
+}
+
+int hip_code(hipError_t e) {
+  if (e == hipSuccess) return KDB_PUT_OK;
+  return (e == hipErrorNoDevice || e == hipErrorInvalidDevice) ? KDB_PUT_ENODEV : KDB_PUT_EHIP;
+}
+
+// Temporaries of one load, freed on every way out.
+struct LoadTemps {
+  FileRec* d_rec = nullptr;
+  ParseFile* d_pf = nullptr;
+  uint32_t* d_tile_file = nullptr;
+  uint32_t* d_tile_count = nullptr;
+  uint64_t* d_tile_prefix = nullptr;
+  uint32_t* d_malformed = nullptr;
+  uint32_t* d_count = nullptr;
+  ~LoadTemps() {
+    dfree(d_rec);
+    dfree(d_pf);
+    dfree(d_tile_file);
+    dfree(d_tile_count);
+    dfree(d_tile_prefix);
+    dfree(d_malformed);
+    dfree(d_count);
+  }
+};
+
+#define KDB_TRY(expr)                     \
+  do {                                    \
+    const hipError_t e_ = (expr);         \
+    if (e_ != hipSuccess) return e_;      \
+  } while (0)
+
+template <class T>
+hipError_t upload(hipStream_t st, T** d, const T* h, size_t n) {
+  KDB_TRY(hipMalloc(reinterpret_cast<void**>(d), std::max<size_t>(n, 1) * sizeof(T)));
+  if (n) KDB_TRY(hipMemcpyAsync(*d, h, n * sizeof(T), hipMemcpyHostToDevice, st));
+  return hipSuccess;
+}
+
+hipError_t index_load(kdb_index* ix, hipStream_t st, const uint8_t* d_files, const uint64_t* file_off,
+                      const uint64_t* file_size, const uint32_t* fileid, uint32_t nfiles, int32_t* file_status,
+                      bool* too_many) {
+  LoadTemps t;
+  ix->d_files = d_files;
+  ix->nfiles = nfiles;
+  ix->fileid.assign(fileid, fileid + nfiles);
+  KDB_TRY(upload(st, &ix->d_file_off, file_off, nfiles));
+  KDB_TRY(upload(st, &ix->d_file_size, file_size, nfiles));
+  KDB_TRY(upload(st, &ix->d_fileid, fileid, nfiles));
+  std::vector<FileRec> rec(nfiles);
+  if (nfiles) {
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_rec), nfiles * sizeof(FileRec)));
+    hipLaunchKernelGGL(index_file_kernel, dim3(nfiles), dim3(kFileBlock), 0, st, d_files, ix->d_file_off,
+                       ix->d_file_size, t.d_rec);
+    KDB_TRY(hipGetLastError());
+    KDB_TRY(hipMemcpyAsync(rec.data(), t.d_rec, nfiles * sizeof(FileRec), hipMemcpyDeviceToHost, st));
+  }
+  KDB_TRY(hipStreamSynchronize(st));
+  std::vector<int32_t> status(nfiles);
+  for (uint32_t f = 0; f < nfiles; f++) status[f] = rec[f].status;
+
+  // LoadDatabase's order (:1007-1014): by (timestamp, fileid)
+  std::vector<uint32_t> order;
+  std::vector<ParseFile> pf;
+  std::vector<uint32_t> tile_file;
+  uint64_t nrows = 0;
+  for (;;) {
+    order.clear();
+    for (uint32_t f = 0; f < nfiles; f++)
+      if (status[f] == 0) order.push_back(f);
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+      if (rec[a].timestamp != rec[b].timestamp) return rec[a].timestamp < rec[b].timestamp;
+      return fileid[a] < fileid[b];
+    });
+    pf.clear();
+    tile_file.clear();
+    nrows = 0;
+    for (uint32_t f : order) {
+      ParseFile p{};
+      p.reg_off = file_off[f] + rec[f].offset_indexes;
+      p.reg_len = file_size[f] - hs::kFooterSize - rec[f].offset_indexes;
+      p.nvar = 2u * rec[f].num_entries;
+      p.row_base = nrows;
+      p.first_tile = (uint32_t)tile_file.size();
+      p.ntiles = (uint32_t)((p.reg_len + kParseTile - 1u) / kParseTile);
+      p.slot = f;
+      nrows += rec[f].num_entries;
+      if (nrows > kMaxRows || tile_file.size() + p.ntiles > 0x7FFFFFFFull) {
+        *too_many = true;
+        return hipSuccess;
+      }
+      tile_file.insert(tile_file.end(), p.ntiles, (uint32_t)pf.size());
+      pf.push_back(p);
+    }
+    dfree(ix->d_row_hash);
+    dfree(ix->d_row_off);
+    dfree(ix->d_row_file);
+    dfree(t.d_pf);
+    dfree(t.d_tile_file);
+    dfree(t.d_tile_count);
+    dfree(t.d_tile_prefix);
+    dfree(t.d_malformed);
+    const uint32_t ntiles = (uint32_t)tile_file.size();
+    if (nrows == 0 || ntiles == 0) break;
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&ix->d_row_hash), nrows * 8u));
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&ix->d_row_off), nrows * 4u));
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&ix->d_row_file), nrows * 4u));
+    KDB_TRY(upload(st, &t.d_pf, pf.data(), pf.size()));
+    KDB_TRY(upload(st, &t.d_tile_file, tile_file.data(), tile_file.size()));
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_tile_count), (size_t)ntiles * 4u));
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_tile_prefix), ((size_t)ntiles + 1u) * 8u));
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_malformed), (size_t)nfiles * 4u));
+    KDB_TRY(hipMemsetAsync(t.d_malformed, 0, (size_t)nfiles * 4u, st));
+    hipLaunchKernelGGL(index_count_kernel, dim3(ntiles), dim3(kParseTile), 0, st, d_files, t.d_pf, t.d_tile_file,
+                       t.d_tile_count);
+    KDB_TRY(hipGetLastError());
+    KDB_TRY(launch_exclusive_scan(st, t.d_tile_count, ntiles, t.d_tile_prefix, t.d_tile_prefix + ntiles));
+    hipLaunchKernelGGL(index_parse_kernel, dim3(ntiles), dim3(kParseTile), 0, st, d_files, t.d_pf, t.d_tile_file,
+                       t.d_tile_prefix, ix->d_row_hash, ix->d_row_off, ix->d_row_file, t.d_malformed);
+    KDB_TRY(hipGetLastError());
+    std::vector<uint32_t> bad(nfiles);
+    KDB_TRY(hipMemcpyAsync(bad.data(), t.d_malformed, (size_t)nfiles * 4u, hipMemcpyDeviceToHost, st));
+    KDB_TRY(hipStreamSynchronize(st));
+    bool again = false;
+    for (uint32_t f = 0; f < nfiles; f++)
+      if (bad[f] && status[f] == 0) {
+        status[f] = -3;       // no row of a malformed array is kept: number the rows again without it
+        again = true;
+      }
+    if (!again) break;
+  }
+  for (uint32_t f = 0; f < nfiles; f++) file_status[f] = status[f];
+  ix->nrows = nrows;
+  if (nrows == 0) return hipSuccess;
+
+  uint64_t B = 2;
+  while (B < 2u * nrows) B <<= 1;
+  ix->nbuckets = B;
+  const uint32_t n = (uint32_t)nrows;
+  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&ix->d_start), (B + 1u) * 8u));
+  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&ix->d_slots), nrows * sizeof(Slot)));
+  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_count), B * 4u));
+  KDB_TRY(hipMemsetAsync(t.d_count, 0, B * 4u, st));
+  const uint32_t g = std::min<uint32_t>((n + 255u) / 256u, 2048u);
+  hipLaunchKernelGGL(index_hist_kernel, dim3(g), dim3(256), 0, st, ix->d_row_hash, n, B - 1u, t.d_count);
+  KDB_TRY(hipGetLastError());
+  KDB_TRY(launch_exclusive_scan(st, t.d_count, (uint32_t)B, ix->d_start, ix->d_start + B));
+  hipLaunchKernelGGL(index_fill_kernel, dim3(g), dim3(256), 0, st, ix->d_row_hash, ix->d_row_off, ix->d_row_file, n,
+                     B - 1u, ix->d_start, t.d_count, ix->d_slots);
+  KDB_TRY(hipGetLastError());
+  return hipStreamSynchronize(st);
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------ C ABI
+extern "C" int kdb_index_create(uint32_t hash_type, kdb_index** ix) {
+  if (!ix || hash_type > 1) return KDB_PUT_EINVAL;
+  kdb_index* p = new (std::nothrow) kdb_index;
+  if (!p) return KDB_PUT_EINVAL;
+  p->hash_type = hash_type;
+  *ix = p;
+  return KDB_PUT_OK;
+}
+
+extern "C" int kdb_index_destroy(kdb_index* ix) {
+  if (!ix) return KDB_PUT_EINVAL;
+  index_release(ix);
+  delete ix;
+  return KDB_PUT_OK;
+}
+
+extern "C" int kdb_index_load_files(kdb_index* ix, void* stream, const uint8_t* d_files, const uint64_t* file_off,
+                                    const uint64_t* file_size, const uint32_t* fileid, uint32_t nfiles,
+                                    int32_t* file_status_out, uint64_t* entries_out) {
+  if (!ix || (nfiles && (!d_files || !file_off || !file_size || !fileid || !file_status_out)))
+    return KDB_PUT_EINVAL;
+  for (uint32_t f = 0; f < nfiles; f++)
+    if (file_size[f] > kMaxFileSize) return KDB_PUT_EINVAL;
+  index_release(ix);
+  bool too_many = false;
+  const hipError_t e = index_load(ix, (hipStream_t)stream, d_files, file_off, file_size, fileid, nfiles,
+                                  file_status_out, &too_many);
+  if (e != hipSuccess || too_many) {
+    index_release(ix);
+    return too_many ? KDB_PUT_EINVAL : hip_code(e);
+  }
+  if (entries_out) *entries_out = ix->nrows;
+  return KDB_PUT_OK;
+}
+
+extern "C" int kdb_index_entry_count(const kdb_index* ix, uint64_t* count) {
+  if (!ix || !count) return KDB_PUT_EINVAL;
+  *count = ix->nrows;
+  return KDB_PUT_OK;
+}
+
+extern "C" int kdb_index_pairs(const kdb_index* ix, uint64_t* hash_out, uint64_t* location_out) {
+  if (!ix || (ix->nrows && (!hash_out || !location_out))) return KDB_PUT_EINVAL;
+  if (ix->nrows == 0) return KDB_PUT_OK;
+  const size_t n = (size_t)ix->nrows;
+  std::vector<uint32_t> off(n), file(n);
+  hipError_t e = hipMemcpy(hash_out, ix->d_row_hash, n * 8u, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(off.data(), ix->d_row_off, n * 4u, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(file.data(), ix->d_row_file, n * 4u, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return hip_code(e);
+  for (size_t r = 0; r < n; r++) {
+    if (file[r] >= ix->nfiles) return KDB_PUT_EHIP;
+    location_out[r] = (uint64_t)ix->fileid[file[r]] << 32 | off[r];
+  }
+  return KDB_PUT_OK;
+}
+
+extern "C" uint64_t kdb_index_get_scratch_bytes(uint32_t n) { return (uint64_t)n * 4u + 256u; }
+
+extern "C" int kdb_index_get_batch(const kdb_index* ix, void* stream, const uint8_t* keys, const uint64_t* key_off,
+                                   const uint32_t* key_len, uint32_t n, int verify_header,
+                                   uint64_t multipart_required, uint8_t* scratch, uint64_t scratch_bytes,
+                                   uint64_t* stored_off, uint64_t* avail, uint64_t* svc, uint64_t* size,
+                                   uint32_t* checksum, uint32_t* checksum_initial, uint64_t* out_off,
+                                   uint64_t* location, int32_t* status, uint64_t* summary) {
+  if (multipart_required == 0) multipart_required = 1048576u;    // internal__size_multipart_required
+  if (!ix || !summary || verify_header < 0 || verify_header > 1 || multipart_required > (1ull << 31) ||
+      scratch_bytes < kdb_index_get_scratch_bytes(n) ||
+      (n && (!keys || !key_off || !key_len || !scratch || !stored_off || !avail || !svc || !size || !checksum ||
+             !checksum_initial || !out_off || !location || !status)))
+    return KDB_PUT_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(summary, 0, 5 * 8, st);
+  if (e != hipSuccess) return hip_code(e);
+  if (n == 0) return KDB_PUT_OK;
+  uint32_t* slot_len = reinterpret_cast<uint32_t*>(scratch);
+  const IndexView view{ix->d_files,  ix->d_file_off, ix->d_file_size,        ix->d_fileid, ix->d_start,
+                       ix->d_slots,  ix->nbuckets ? ix->nbuckets - 1u : 0u, (uint32_t)ix->nrows, ix->hash_type};
+  const uint32_t waves = kGetBlock / 64;
+  const uint32_t g = std::min<uint32_t>((n + waves - 1u) / waves, 16384u);
+  hipLaunchKernelGGL(index_get_kernel, dim3(g), dim3(kGetBlock), 0, st, view, keys, key_off, key_len, n,
+                     verify_header, multipart_required, stored_off, avail, svc, size, checksum, checksum_initial,
+                     slot_len, location, status);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = launch_exclusive_scan(st, slot_len, n, out_off, summary + 1);
+  if (e != hipSuccess) return hip_code(e);
+  const uint32_t sg = std::min<uint32_t>((n + 255u) / 256u, 1024u);
+  hipLaunchKernelGGL(index_summary_kernel, dim3(sg), dim3(256), 0, st, avail, size, status, n,
+                     reinterpret_cast<unsigned long long*>(summary));
+  return hip_code(hipGetLastError());
+}

@@ -1,0 +1,207 @@
+"""Get by key on the GPU (include/kdb_put.h, csrc/index.hip): the index over a
+set of closed HSTable files and the batched lookup in front of the decoder.
+
+  HSTableIndex(files)     uploads the files once and loads their offset arrays
+                          (HSTableManager::LoadDatabase / LoadFile)
+  .get(keys, verify)      [(status, value bytes)]: StorageEngine::GetWithIndex /
+                          GetEntry per key, then kdb_get_values_batch over the
+                          resident files (Database::GetRaw)
+  .locate(keys)           the lookup alone: (locations, statuses)
+
+status: 0 OK, NOTFOUND, DELETED (Database::Get reports NotFound), MULTIPART
+(MultipartRequired), or the decoder's -1 / -2 (see get.py).  Databases opened
+with compression enabled only; files without a usable footer are not
+recovered (`.file_status`).
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from .lz4 import DeviceBuffer, Stream
+
+NOTFOUND, DELETED, MULTIPART = -3, -4, -5
+MULTIPART_REQUIRED = 1 << 20     # internal__size_multipart_required
+
+
+def lib():
+    return _lib.load()
+
+
+def _a8(x: int) -> int:
+    return (x + 7) & ~7
+
+
+class _Lookup:
+    """Device arrays of one batch of n lookups (inputs, outputs, the decoder's outputs)."""
+
+    FIELDS = (("key_off", 8), ("stored_off", 8), ("avail", 8), ("svc", 8), ("size", 8), ("out_off", 8),
+              ("location", 8), ("out_len", 8), ("key_len", 4), ("checksum", 4), ("checksum_initial", 4),
+              ("status", 4), ("dstatus", 4))
+
+    def __init__(self, n: int, key_bytes: int):
+        self.n = n
+        self.off = {}
+        o = 0
+        for name, w in self.FIELDS:
+            self.off[name] = o
+            o += _a8(n * w)
+        self.off["summary"] = o
+        self.meta = DeviceBuffer(o + 40)
+        self.keys = DeviceBuffer(key_bytes + 64)
+        self.scratch_bytes = int(lib().kdb_index_get_scratch_bytes(n))
+        self.scratch = DeviceBuffer(self.scratch_bytes)
+
+    def p(self, name: str) -> int:
+        return self.meta.ptr + self.off[name]
+
+    def free(self) -> None:
+        for b in (self.meta, self.keys, self.scratch):
+            b.free()
+
+
+class HSTableIndex:
+    def __init__(self, files: dict[str, bytes], hash_type: int = 1, stream: Stream | None = None):
+        self.names = sorted(files)
+        self.hash_type = hash_type
+        n = len(self.names)
+        size = np.array([len(files[f]) for f in self.names], np.uint64)
+        off = np.zeros(n, np.uint64)
+        if n > 1:
+            off[1:] = np.cumsum((size[:-1] + 63) & ~np.uint64(63))
+        total = int(off[-1] + size[-1]) if n else 0
+        buf = np.zeros(total + 64, np.uint8)
+        for f, o in zip(self.names, off):
+            buf[int(o):int(o) + len(files[f])] = np.frombuffer(files[f], np.uint8)
+        self.file_off, self.file_size = off, size
+        self.fileid = np.array([int(f, 16) for f in self.names], np.uint32)
+        self.files = DeviceBuffer(total + 64)
+        self.h = None
+        st = stream.ptr if stream else None
+        self.files.upload(buf, stream=st)
+        h = ctypes.c_void_p()
+        _lib.check(lib().kdb_index_create(hash_type, ctypes.byref(h)), "kdb_index_create")
+        self.h = h.value
+        status = np.zeros(max(n, 1), np.int32)
+        entries = ctypes.c_uint64(0)
+        _lib.check(lib().kdb_index_load_files(self.h, st, self.files.ptr, off.ctypes.data, size.ctypes.data,
+                                              self.fileid.ctypes.data, n, status.ctypes.data, ctypes.byref(entries)),
+                   "kdb_index_load_files")
+        self.file_status = {f: int(s) for f, s in zip(self.names, status[:n])}
+        self.entries = entries.value
+
+    def pairs(self) -> tuple[np.ndarray, np.ndarray]:
+        """The loaded rows in sequence order: (hashed keys, fileid << 32 | offset)."""
+        h = np.zeros(max(self.entries, 1), np.uint64)
+        loc = np.zeros(max(self.entries, 1), np.uint64)
+        _lib.check(lib().kdb_index_pairs(self.h, h.ctypes.data, loc.ctypes.data), "kdb_index_pairs")
+        return h[:self.entries], loc[:self.entries]
+
+    def _lookup(self, keys, st, verify_header: int, multipart_required: int) -> _Lookup:
+        n = len(keys)
+        klen = np.array([len(k) for k in keys], np.uint32)
+        koff = np.zeros(n, np.uint64)
+        if n > 1:
+            koff[1:] = np.cumsum(klen[:-1].astype(np.uint64))
+        kbuf = np.frombuffer(b"".join(keys), np.uint8)
+        L = _Lookup(n, len(kbuf))
+        try:
+            if len(kbuf):
+                L.keys.upload(kbuf, stream=st)
+            L.meta.upload(koff, L.off["key_off"], stream=st)
+            L.meta.upload(klen, L.off["key_len"], stream=st)
+            self.run_lookup(L, st, n, verify_header, multipart_required)
+        except Exception:
+            L.free()
+            raise
+        return L
+
+    def run_lookup(self, L: _Lookup, st, n: int, verify_header: int = 0,
+                   multipart_required: int = MULTIPART_REQUIRED) -> None:
+        """kdb_index_get_batch on keys already resident in `L`."""
+        _lib.check(lib().kdb_index_get_batch(
+            self.h, st, L.keys.ptr, L.p("key_off"), L.p("key_len"), n, verify_header, multipart_required,
+            L.scratch.ptr, L.scratch_bytes, L.p("stored_off"), L.p("avail"), L.p("svc"), L.p("size"),
+            L.p("checksum"), L.p("checksum_initial"), L.p("out_off"), L.p("location"), L.p("status"),
+            L.p("summary")), "kdb_index_get_batch")
+
+    def decode_plan(self, L: _Lookup, st, n: int, frame_cap: int | None = None):
+        """The summary download: (found, out bytes, frame_cap, max_in, max_out)."""
+        s = L.meta.download(40, L.off["summary"], dtype=np.uint64, stream=st)
+        found, out_bytes, max_avail, max_size, slots = (int(x) for x in s)
+        if frame_cap is None:
+            # frames are >= 8 bytes, so `slots` always suffices; values KingDB
+            # writes hold one frame per part, far fewer (see get.get_values)
+            frame_cap = min(slots, 2 * n + 8 * (slots - n) // 4096 + 64)
+        return found, out_bytes, frame_cap, max_avail, max_size
+
+    def run_decode(self, L: _Lookup, st, n: int, verify: int, out: DeviceBuffer, scratch: DeviceBuffer,
+                   frame_cap: int, max_in: int, max_out: int) -> None:
+        _lib.check(lib().kdb_get_values_batch(
+            st, self.files.ptr, L.p("stored_off"), L.p("avail"), L.p("svc"), L.p("size"), n, out.ptr,
+            L.p("out_off"), verify, L.p("checksum"), L.p("checksum_initial"), frame_cap, max_in, max_out,
+            scratch.ptr, scratch.nbytes, L.p("out_len"), L.p("dstatus")), "kdb_get_values_batch")
+
+    def locate(self, keys, verify_header: int = 0, stream: Stream | None = None,
+               multipart_required: int = MULTIPART_REQUIRED) -> tuple[np.ndarray, np.ndarray]:
+        n = len(keys)
+        if n == 0:
+            return np.zeros(0, np.uint64), np.zeros(0, np.int32)
+        st = stream.ptr if stream else None
+        L = self._lookup(keys, st, verify_header, multipart_required)
+        try:
+            loc = L.meta.download(8 * n, L.off["location"], dtype=np.uint64, stream=st)
+            status = L.meta.download(4 * n, L.off["status"], dtype=np.int32, stream=st)
+            return loc, status
+        finally:
+            L.free()
+
+    def get(self, keys, verify: int = 0, stream: Stream | None = None,
+            multipart_required: int = MULTIPART_REQUIRED, frame_cap: int | None = None
+            ) -> list[tuple[int, bytes]]:
+        n = len(keys)
+        if n == 0:
+            return []
+        st = stream.ptr if stream else None
+        L = self._lookup(keys, st, 1 if verify else 0, multipart_required)
+        out = scratch = None
+        try:
+            found, out_bytes, frame_cap, max_in, max_out = self.decode_plan(L, st, n, frame_cap)
+            status = L.meta.download(4 * n, L.off["status"], dtype=np.int32, stream=st)
+            if found == 0:
+                return [(int(s), b"") for s in status]
+            out = DeviceBuffer(out_bytes + 64)
+            scratch = DeviceBuffer(int(lib().kdb_get_scratch_bytes(n, frame_cap)))
+            self.run_decode(L, st, n, verify, out, scratch, frame_cap, max_in, max_out)
+            lo, hi = L.off["out_off"], L.off["out_len"] + 8 * n
+            m = L.meta.download(hi - lo, lo, stream=st)
+            ooff = m[:8 * n].view(np.uint64)
+            olen = m[L.off["out_len"] - lo:][:8 * n].view(np.uint64)
+            dstatus = L.meta.download(4 * n, L.off["dstatus"], dtype=np.int32, stream=st)
+            data = out.download(out_bytes, stream=st)
+            res = []
+            for i in range(n):
+                if status[i] != 0:
+                    res.append((int(status[i]), b""))
+                else:
+                    res.append((int(dstatus[i]), data[int(ooff[i]):int(ooff[i]) + int(olen[i])].tobytes()))
+            return res
+        finally:
+            L.free()
+            for b in (out, scratch):
+                if b is not None:
+                    b.free()
+
+    def close(self) -> None:
+        if self.h:
+            lib().kdb_index_destroy(self.h)
+            self.h = None
+        self.files.free()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
