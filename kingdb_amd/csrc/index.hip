@@ -33,6 +33,19 @@
 //                        (hstable_decode.h), key compare and crc32c(key) on the lanes
 //   scan                 64-byte-aligned output slots
 //   index_summary_kernel what the host needs to size the decode
+// Scan (include/kdb_scan.h; Database::NewIterator, interface/iterator.h:112-214):
+//   index_live_kernel    wave per row: the row is live iff the lookup of its
+//                        own stored key would select it (prepare, synchronous)
+//   scan / index_live_scatter_kernel
+//                        the live rows compacted in sequence order into a list
+//                        of file rank << 32 | offset: iterator order when every
+//                        file's rows ascend
+//   index_bitonic_kernel the cold path when they do not: a global-memory
+//                        bitonic network over the list padded with ~0
+//   scan                 the live keys' lengths -> their places in the packed keys
+//   index_scan_emit_kernel
+//                        wave per live row of a window: the lookup's outputs
+//                        for that entry, and its key (stream-ordered)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -430,6 +443,250 @@ __global__ __launch_bounds__(256) void index_summary_kernel(const uint64_t* __re
   }
 }
 
+// ------------------------------------------------------------------ scan
+// One candidate's first bytes staged in the wave's LDS row and decoded there:
+// locate_entry() on a copy.  A header is at most kMaxEntryHeader <=
+// kHeaderStage bytes, so decoding min(room, kHeaderStage) bytes is decoding
+// all `room` of them.  False where the entry does not decode or validate.
+__device__ __forceinline__ bool stage_entry_header(const uint8_t* file, uint64_t fs, uint32_t offset,
+                                                   int verify_header, uint8_t* s_hdr, uint32_t lane,
+                                                   hs::EntryHeader* hd) {
+  const uint64_t room = offset < fs ? min(fs - offset, (uint64_t)kHeaderStage) : 0u;
+  wave_lds_sync();
+  if (lane < room) s_hdr[lane] = file[(uint64_t)offset + lane];
+  wave_lds_sync();
+  return room != 0 && hs::decode_entry_header(s_hdr, room, verify_header != 0, hd) == hs::kDecodeOk &&
+         hs::entry_valid(*hd, offset, fs);
+}
+
+// The candidate walk of index_get_kernel, for the scan's liveness pass: among the slots of h's bucket whose hash equals h and whose
+// packed rank (seq + 1) << 32 | position lies above `floor`, newest first, the
+// first whose header decodes, is valid (GetWithIndex:446 skips the others) and
+// whose stored key equals key[0 .. klen).  floor 0 takes every row;
+// (r + 1) << 32 | 0xFFFFFFFF only the rows newer than row r.
+// A second copy of the walk, on purpose: with index_get_kernel calling this
+// function instead of its own loop, `locate` measured 3.55-3.57 ms against the
+// 3.52-3.53 ms of the unchanged kernel, interleaved on one device (126 VGPRs
+// against 125, another spill pattern), which is outside that kernel's own
+// run-to-run spread.  So the lookup keeps its text.
+__device__ __forceinline__ bool find_candidate(const IndexView& ix, uint64_t h, const uint8_t* key, uint32_t klen,
+                                               uint64_t floor, int verify_header, uint8_t* s_hdr, uint32_t lane,
+                                               Slot* c_out, hs::EntryHeader* hd_out, uint64_t* fo_out) {
+  if (ix.nrows == 0) return false;
+  const uint64_t b = h & ix.mask;
+  const uint64_t s0 = ix.start[b], s1 = ix.start[b + 1u];
+  uint64_t bound = ~0ull;               // candidates taken so far have (seq + 1) << 32 | slot >= bound
+  for (;;) {
+    uint64_t best = floor;
+    for (uint64_t i = s0 + lane; i < s1; i += 64u) {
+      const Slot s = ix.slots[i];
+      const uint64_t pk = ((uint64_t)s.seq + 1u) << 32 | (uint32_t)(i - s0);
+      if (s.hash == h && pk < bound && pk > best) best = pk;
+    }
+    best = wave_max64(best);
+    if (best == floor) return false;
+    bound = best;
+    const Slot c = ix.slots[s0 + (uint32_t)best];
+    const uint64_t fo = ix.file_off[c.file], fs = ix.file_size[c.file];
+    const uint8_t* file = ix.files + fo;
+    hs::EntryHeader hd;
+    if (!stage_entry_header(file, fs, c.offset, verify_header, s_hdr, lane, &hd)) continue;
+    if (hd.size_key != klen) continue;
+    // locate_entry: [offset + size_header, + size_key) lies inside the file
+    const uint8_t* stored_key = file + c.offset + hd.size_header;
+    bool diff = false;
+    for (uint32_t o = 4u * lane; o < klen; o += 256u) {
+      if (o + 4u <= klen) {
+        diff |= *reinterpret_cast<const u32u*>(stored_key + o) != *reinterpret_cast<const u32u*>(key + o);
+      } else {
+        for (uint32_t j = o; j < klen; j++) diff |= stored_key[j] != key[j];
+      }
+    }
+    if (ballot(diff) != 0) continue;
+    *c_out = c;
+    *hd_out = hd;
+    *fo_out = fo;
+    return true;
+  }
+}
+
+// What the scan needs beside the lookup's view: the rows in sequence order
+// and the files' ranks in that order.
+struct RowView {
+  const uint64_t* hash;
+  const uint32_t* off;
+  const uint32_t* file;      // file slot
+  const uint32_t* file_rank; // file slot -> rank in (timestamp, fileid) order
+};
+
+// stats: [0] some row's offset is not above its predecessor's in the same
+// file, [1] key bytes of the live rows, [2] their longest key.
+//
+// Wave per row r: the row is live iff the lookup of its own stored key would
+// select it.  Its entry decodes, is valid and is no delete; the hash of the
+// stored key is the row's hash (else Get cannot reach the row); and no newer
+// equal-hash row holds a valid entry with the same key.  klen[r] = the key's
+// length for a live row, 0 for a dead one (a valid entry's key is not empty).
+__global__ __launch_bounds__(kGetBlock) void index_live_kernel(IndexView ix, RowView rows, int verify_header,
+                                                               uint32_t* __restrict__ flag,
+                                                               uint32_t* __restrict__ klen_out,
+                                                               unsigned long long* __restrict__ stats) {
+  __shared__ uint8_t s_key[kGetBlock / 64][kKeyStage];
+  __shared__ uint8_t s_hdr[kGetBlock / 64][kHeaderStage];
+  const uint32_t lane = lane_id();
+  const uint32_t wib = threadIdx.x / 64u;
+  const uint32_t nw = gridDim.x * (kGetBlock / 64);
+  uint64_t bytes = 0;
+  uint32_t longest = 0;
+  bool unordered = false;
+  for (uint32_t r = blockIdx.x * (kGetBlock / 64) + wib; r < ix.nrows; r += nw) {
+    const uint32_t f = uni(rows.file[r]), off = uni(rows.off[r]);
+    const uint64_t h = rows.hash[r];
+    if (r > 0 && rows.file[r - 1u] == f && rows.off[r - 1u] >= off) unordered = true;
+    const uint64_t fo = ix.file_off[f], fs = ix.file_size[f];
+    const uint8_t* file = ix.files + fo;
+    uint32_t live_len = 0;
+    hs::EntryHeader hd;
+    if (stage_entry_header(file, fs, off, verify_header, s_hdr[wib], lane, &hd) &&
+        (hd.flags & hs::kTypeDelete) == 0) {
+      // entry_valid: the key lies inside the file, so its length fits 32 bits
+      const uint32_t klen = (uint32_t)hd.size_key;
+      const uint8_t* key = file + off + hd.size_header;
+      if (klen <= kKeyStage) {
+        for (uint32_t i = lane; i < klen; i += 64u) s_key[wib][i] = key[i];
+        wave_lds_sync();
+        key = s_key[wib];
+      }
+      const uint64_t hk = ix.hash_type == 1 ? xxh64(key, klen) : murmur3_64(key, klen);
+      Slot c;
+      hs::EntryHeader ch;
+      uint64_t cfo;
+      // no newer equal-hash row (the common case): live without a second header read
+      if (hk == h && !find_candidate(ix, h, key, klen, ((uint64_t)r + 1u) << 32 | 0xFFFFFFFFull, verify_header,
+                                     s_hdr[wib], lane, &c, &ch, &cfo))
+        live_len = klen;
+    }
+    if (lane == 0) {
+      flag[r] = live_len != 0;
+      klen_out[r] = live_len;
+    }
+    bytes += live_len;
+    longest = live_len > longest ? live_len : longest;
+  }
+  if (lane == 0) {                      // one atomic per wave and field
+    if (unordered) atomicOr(&stats[0], 1ull);
+    if (bytes) atomicAdd(&stats[1], (unsigned long long)bytes);
+    if (longest) atomicMax(&stats[2], (unsigned long long)longest);
+  }
+}
+
+// Live row r goes to position pos[r] of the live list: rank << 32 | offset,
+// so that the list's order is the iterator's and a sort needs no second key.
+__global__ void index_live_scatter_kernel(RowView rows, uint32_t n, const uint32_t* __restrict__ flag,
+                                          const uint32_t* __restrict__ klen, const uint64_t* __restrict__ pos,
+                                          uint64_t* __restrict__ list, uint32_t* __restrict__ list_klen) {
+  for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x) {
+    if (!flag[r]) continue;
+    const uint64_t at = pos[r];
+    list[at] = (uint64_t)rows.file_rank[rows.file[r]] << 32 | rows.off[r];
+    list_klen[at] = klen[r];
+  }
+}
+
+// One compare-exchange step (k, j) of the bitonic network over n = 2^m keys
+// (the list padded with ~0), the key lengths carried along.
+__global__ void index_bitonic_kernel(uint64_t* __restrict__ key, uint32_t* __restrict__ val, uint32_t n, uint32_t k,
+                                     uint32_t j) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const uint32_t p = i ^ j;
+    if (p <= i) continue;               // the lower index of a pair does the work; p < n as j < n = 2^m
+    const uint64_t a = key[i], b = key[p];
+    const bool up = (i & k) == 0;
+    if (up ? a > b : a < b) {
+      key[i] = b;
+      key[p] = a;
+      const uint32_t va = val[i], vb = val[p];
+      val[i] = vb;
+      val[p] = va;
+    }
+  }
+}
+
+// Wave per live row of the window [first, first + n): the header decoded
+// again, the outputs of index_get_kernel for that entry, its key's length and
+// place in the packed keys, and the key bytes.
+__global__ __launch_bounds__(kGetBlock) void index_scan_emit_kernel(
+    IndexView ix, const uint64_t* __restrict__ list, const uint32_t* __restrict__ rank_file,
+    const uint64_t* __restrict__ key_prefix, uint64_t first, uint32_t n, uint64_t multipart_required,
+    uint8_t* __restrict__ keys_out, uint64_t* __restrict__ key_off, uint32_t* __restrict__ key_len,
+    uint64_t* __restrict__ stored_off, uint64_t* __restrict__ avail, uint64_t* __restrict__ svc,
+    uint64_t* __restrict__ size, uint32_t* __restrict__ checksum, uint32_t* __restrict__ checksum_initial,
+    uint32_t* __restrict__ slot_len, uint64_t* __restrict__ location, int32_t* __restrict__ status) {
+  __shared__ uint32_t s_t[256];
+  __shared__ uint8_t s_hdr[kGetBlock / 64][kHeaderStage];
+  crc::stage_table(s_t);
+  __syncthreads();
+  const uint32_t lane = lane_id();
+  const uint32_t wib = threadIdx.x / 64u;
+  const uint32_t nw = gridDim.x * (kGetBlock / 64);
+  const uint64_t base = key_prefix[first];
+  for (uint32_t v = blockIdx.x * (kGetBlock / 64) + wib; v < n; v += nw) {
+    const uint64_t e = list[first + v];
+    const uint32_t f = uni(rank_file[(uint32_t)(e >> 32)]), off = uni((uint32_t)e);
+    const uint64_t ko = key_prefix[first + v] - base;
+    const uint32_t klen = uni((uint32_t)(key_prefix[first + v + 1u] - key_prefix[first + v]));
+    const uint64_t fo = ix.file_off[f], fs = ix.file_size[f];
+    const uint8_t* file = ix.files + fo;
+    int32_t st = KDB_GET_NOTFOUND;
+    uint64_t o_stored = 0, o_avail = 0, o_svc = 0, o_size = 0, o_loc = 0;
+    uint32_t o_ck = 0, o_ci = 0, o_klen = 0;
+    hs::EntryHeader hd;
+    // the entry prepare() found live; the files have not changed since, so it
+    // decodes to the same header (checked all the same: its key must be the
+    // klen bytes the prepared prefix reserved)
+    if (stage_entry_header(file, fs, off, 0, s_hdr[wib], lane, &hd) && hd.size_key == klen) {
+      const uint8_t* key = file + off + hd.size_header;
+      uint8_t* dst = keys_out + ko;
+      for (uint32_t o = 4u * lane; o < klen; o += 256u) {
+        if (o + 4u <= klen) {
+          *reinterpret_cast<u32u*>(dst + o) = *reinterpret_cast<const u32u*>(key + o);
+        } else {
+          for (uint32_t j = o; j < klen; j++) dst[j] = key[j];
+        }
+      }
+      o_klen = klen;
+      o_loc = (uint64_t)ix.fileid[f] << 32 | off;
+      if (hs::is_compressed(hd) && hd.size_value > multipart_required) {   // the lookup's rule
+        st = KDB_GET_MULTIPART;
+      } else {
+        st = 0;
+        uint64_t svo = 0;
+        hs::size_value_offset(hd, &svo);
+        o_stored = fo + off + hd.size_header + klen;
+        o_avail = svo;
+        o_svc = hd.size_value_compressed;
+        o_size = hd.size_value;
+        o_ck = hd.checksum_content;
+        const BytesMsg msg{key};
+        o_ci = crc::extend_wave(0u, klen, msg, s_t);          // storage_engine.h:497-500
+      }
+    }
+    if (lane == 0) {
+      key_off[v] = ko;
+      key_len[v] = o_klen;
+      stored_off[v] = o_stored;
+      avail[v] = o_avail;
+      svc[v] = o_svc;
+      size[v] = o_size;
+      checksum[v] = o_ck;
+      checksum_initial[v] = o_ci;
+      slot_len[v] = (uint32_t)((o_size + 63u) & ~63ull);
+      location[v] = o_loc;
+      status[v] = st;
+    }
+  }
+}
+
 }  // namespace
 }  // namespace kdb_lz4
 
@@ -448,7 +705,18 @@ struct kdb_index {
   uint64_t* d_row_hash = nullptr;
   uint32_t* d_row_off = nullptr;
   uint32_t* d_row_file = nullptr;
+  uint32_t* d_file_rank = nullptr;       // file slot -> rank in (timestamp, fileid) order
+  uint32_t* d_rank_file = nullptr;       // and back
   std::vector<uint32_t> fileid;
+  // the scan's live list (kdb_index_scan_prepare): rank << 32 | offset in
+  // iterator order, and the exclusive sum of the live keys' lengths (live + 1
+  // entries, on the device for the emit and on the host for the window checks)
+  bool scan_ready = false;
+  uint64_t live = 0;
+  uint32_t sort_steps = 0;
+  uint64_t* d_live = nullptr;
+  uint64_t* d_key_prefix = nullptr;
+  std::vector<uint64_t> key_prefix;
 };
 
 namespace {
@@ -459,7 +727,19 @@ void dfree(T*& p) {
   p = nullptr;
 }
 
+void scan_release(kdb_index* ix) {
+  dfree(ix->d_live);
+  dfree(ix->d_key_prefix);
+  ix->key_prefix.clear();
+  ix->scan_ready = false;
+  ix->live = 0;
+  ix->sort_steps = 0;
+}
+
 void index_release(kdb_index* ix) {
+  scan_release(ix);
+  dfree(ix->d_file_rank);
+  dfree(ix->d_rank_file);
   dfree(ix->d_file_off);
   dfree(ix->d_file_size);
   dfree(ix->d_fileid);
@@ -605,6 +885,17 @@ hipError_t index_load(kdb_index* ix, hipStream_t st, const uint8_t* d_files, con
     if (!again) break;
   }
   for (uint32_t f = 0; f < nfiles; f++) file_status[f] = status[f];
+  {
+    // the scan orders by the file's rank; a file that did not load has no rows and no rank
+    std::vector<uint32_t> rank(nfiles, 0xFFFFFFFFu), rank_file(nfiles, 0u);
+    for (uint32_t i = 0; i < order.size(); i++) {
+      rank[order[i]] = i;
+      rank_file[i] = order[i];
+    }
+    KDB_TRY(upload(st, &ix->d_file_rank, rank.data(), nfiles));
+    KDB_TRY(upload(st, &ix->d_rank_file, rank_file.data(), nfiles));
+    KDB_TRY(hipStreamSynchronize(st));     // the vectors go out of scope
+  }
   ix->nrows = nrows;
   if (nrows == 0) return hipSuccess;
 
@@ -712,6 +1003,161 @@ extern "C" int kdb_index_get_batch(const kdb_index* ix, void* stream, const uint
   hipLaunchKernelGGL(index_get_kernel, dim3(g), dim3(kGetBlock), 0, st, view, keys, key_off, key_len, n,
                      verify_header, multipart_required, stored_off, avail, svc, size, checksum, checksum_initial,
                      slot_len, location, status);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = launch_exclusive_scan(st, slot_len, n, out_off, summary + 1);
+  if (e != hipSuccess) return hip_code(e);
+  const uint32_t sg = std::min<uint32_t>((n + 255u) / 256u, 1024u);
+  hipLaunchKernelGGL(index_summary_kernel, dim3(sg), dim3(256), 0, st, avail, size, status, n,
+                     reinterpret_cast<unsigned long long*>(summary));
+  return hip_code(hipGetLastError());
+}
+
+// ------------------------------------------------------------------ scan
+namespace {
+
+// Temporaries of one prepare, freed on every way out.
+struct ScanTemps {
+  uint32_t* d_flag = nullptr;
+  uint32_t* d_klen = nullptr;
+  uint64_t* d_pos = nullptr;             // nrows + 1: the last is the live count
+  unsigned long long* d_stats = nullptr;
+  uint32_t* d_list_klen = nullptr;
+  ~ScanTemps() {
+    dfree(d_flag);
+    dfree(d_klen);
+    dfree(d_pos);
+    dfree(d_stats);
+    dfree(d_list_klen);
+  }
+};
+
+IndexView view_of(const kdb_index* ix) {
+  return IndexView{ix->d_files, ix->d_file_off, ix->d_file_size,        ix->d_fileid, ix->d_start,
+                   ix->d_slots, ix->nbuckets ? ix->nbuckets - 1u : 0u, (uint32_t)ix->nrows, ix->hash_type};
+}
+
+hipError_t scan_prepare(kdb_index* ix, hipStream_t st, int verify_header, uint64_t* stats_out) {
+  ScanTemps t;
+  const uint32_t n = (uint32_t)ix->nrows;
+  unsigned long long stats[3] = {0, 0, 0};
+  uint64_t live = 0;
+  if (n) {
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_flag), (size_t)n * 4u));
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_klen), (size_t)n * 4u));
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_pos), ((size_t)n + 1u) * 8u));
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_stats), sizeof stats));
+    KDB_TRY(hipMemsetAsync(t.d_stats, 0, sizeof stats, st));
+    const RowView rows{ix->d_row_hash, ix->d_row_off, ix->d_row_file, ix->d_file_rank};
+    const uint32_t waves = kGetBlock / 64;
+    const uint32_t g = std::min<uint32_t>((n + waves - 1u) / waves, 16384u);
+    hipLaunchKernelGGL(index_live_kernel, dim3(g), dim3(kGetBlock), 0, st, view_of(ix), rows, verify_header,
+                       t.d_flag, t.d_klen, t.d_stats);
+    KDB_TRY(hipGetLastError());
+    KDB_TRY(launch_exclusive_scan(st, t.d_flag, n, t.d_pos, t.d_pos + n));
+    KDB_TRY(hipMemcpyAsync(&live, t.d_pos + n, 8, hipMemcpyDeviceToHost, st));
+    KDB_TRY(hipMemcpyAsync(stats, t.d_stats, sizeof stats, hipMemcpyDeviceToHost, st));
+    KDB_TRY(hipStreamSynchronize(st));
+    // iterator order is (file rank, offset): the compaction gives it unless
+    // some file's rows do not ascend; then the list is sorted, padded to a
+    // power of two with ~0
+    uint64_t cap = live;
+    if (stats[0] && live > 1) {
+      cap = 2;
+      while (cap < live) cap <<= 1;
+    }
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&ix->d_live), std::max<uint64_t>(cap, 1) * 8u));
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_list_klen), std::max<uint64_t>(cap, 1) * 4u));
+    if (cap > live) {
+      KDB_TRY(hipMemsetAsync(ix->d_live, 0xFF, cap * 8u, st));
+      KDB_TRY(hipMemsetAsync(t.d_list_klen, 0, cap * 4u, st));
+    }
+    const uint32_t sg = std::min<uint32_t>((n + 255u) / 256u, 2048u);
+    hipLaunchKernelGGL(index_live_scatter_kernel, dim3(sg), dim3(256), 0, st, rows, n, t.d_flag, t.d_klen, t.d_pos,
+                       ix->d_live, t.d_list_klen);
+    KDB_TRY(hipGetLastError());
+    if (cap > live || (stats[0] && live > 1)) {
+      const uint32_t m = (uint32_t)cap;
+      const uint32_t bg = std::min<uint32_t>((m + 255u) / 256u, 2048u);
+      for (uint32_t k = 2; k != 0 && k <= m; k <<= 1)
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+          hipLaunchKernelGGL(index_bitonic_kernel, dim3(bg), dim3(256), 0, st, ix->d_live, t.d_list_klen, m, k, j);
+          ix->sort_steps++;
+        }
+      KDB_TRY(hipGetLastError());
+    }
+  }
+  ix->live = live;
+  ix->key_prefix.assign((size_t)live + 1u, 0);
+  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&ix->d_key_prefix), ((size_t)live + 1u) * 8u));
+  if (live) {
+    KDB_TRY(launch_exclusive_scan(st, t.d_list_klen, (uint32_t)live, ix->d_key_prefix, ix->d_key_prefix + live));
+    KDB_TRY(hipMemcpyAsync(ix->key_prefix.data(), ix->d_key_prefix, ((size_t)live + 1u) * 8u,
+                           hipMemcpyDeviceToHost, st));
+  } else {
+    KDB_TRY(hipMemsetAsync(ix->d_key_prefix, 0, 8, st));
+  }
+  KDB_TRY(hipStreamSynchronize(st));
+  stats_out[0] = live;
+  stats_out[1] = stats[1];
+  stats_out[2] = stats[2];
+  return hipSuccess;
+}
+
+}  // namespace
+
+extern "C" int kdb_index_scan_prepare(kdb_index* ix, void* stream, int verify_header, uint64_t* live,
+                                      uint64_t* key_bytes, uint32_t* max_key_len) {
+  if (!ix || verify_header < 0 || verify_header > 1) return KDB_PUT_EINVAL;
+  scan_release(ix);
+  uint64_t stats[3] = {0, 0, 0};
+  const hipError_t e = scan_prepare(ix, (hipStream_t)stream, verify_header, stats);
+  if (e != hipSuccess) {
+    scan_release(ix);
+    return hip_code(e);
+  }
+  // the list's own sum of key lengths and the liveness pass's must agree
+  if (ix->key_prefix.back() != stats[1]) {
+    scan_release(ix);
+    return KDB_PUT_EHIP;
+  }
+  ix->scan_ready = true;
+  if (live) *live = stats[0];
+  if (key_bytes) *key_bytes = stats[1];
+  if (max_key_len) *max_key_len = (uint32_t)stats[2];
+  return KDB_PUT_OK;
+}
+
+extern "C" int kdb_index_scan_sort_steps(const kdb_index* ix, uint32_t* steps) {
+  if (!ix || !steps || !ix->scan_ready) return KDB_PUT_EINVAL;
+  *steps = ix->sort_steps;
+  return KDB_PUT_OK;
+}
+
+extern "C" uint64_t kdb_index_scan_scratch_bytes(uint32_t n) { return (uint64_t)n * 4u + 256u; }
+
+extern "C" int kdb_index_scan_batch(const kdb_index* ix, void* stream, uint64_t first, uint32_t n,
+                                    uint64_t multipart_required, void* scratch, uint64_t scratch_bytes,
+                                    uint8_t* keys_out, uint64_t keys_cap, uint64_t* key_off, uint32_t* key_len,
+                                    uint64_t* stored_off, uint64_t* avail, uint64_t* svc, uint64_t* size,
+                                    uint32_t* checksum, uint32_t* checksum_initial, uint64_t* out_off,
+                                    uint64_t* location, int32_t* status, uint64_t* summary) {
+  if (multipart_required == 0) multipart_required = 1048576u;    // internal__size_multipart_required
+  if (!ix || !ix->scan_ready || !summary || first > ix->live || n > ix->live - first ||
+      scratch_bytes < kdb_index_scan_scratch_bytes(n) ||
+      (n && (!scratch || !keys_out || !key_off || !key_len || !stored_off || !avail || !svc || !size || !checksum ||
+             !checksum_initial || !out_off || !location || !status)))
+    return KDB_PUT_EINVAL;
+  if (ix->key_prefix[first + n] - ix->key_prefix[first] > keys_cap) return KDB_PUT_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(summary, 0, 5 * 8, st);
+  if (e != hipSuccess) return hip_code(e);
+  if (n == 0) return KDB_PUT_OK;
+  uint32_t* slot_len = reinterpret_cast<uint32_t*>(scratch);
+  const uint32_t waves = kGetBlock / 64;
+  const uint32_t g = std::min<uint32_t>((n + waves - 1u) / waves, 16384u);
+  hipLaunchKernelGGL(index_scan_emit_kernel, dim3(g), dim3(kGetBlock), 0, st, view_of(ix), ix->d_live,
+                     ix->d_rank_file, ix->d_key_prefix, first, n, multipart_required, keys_out, key_off, key_len,
+                     stored_off, avail, svc, size, checksum, checksum_initial, slot_len, location, status);
   e = hipGetLastError();
   if (e == hipSuccess) e = launch_exclusive_scan(st, slot_len, n, out_off, summary + 1);
   if (e != hipSuccess) return hip_code(e);

@@ -7,6 +7,10 @@ set of closed HSTable files and the batched lookup in front of the decoder.
                           GetEntry per key, then kdb_get_values_batch over the
                           resident files (Database::GetRaw)
   .locate(keys)           the lookup alone: (locations, statuses)
+  .scan(first, count)     a window of the live entries in iterator order
+                          (Database::NewIterator): [(key, status, value)]
+  .items(batch)           a generator over all of them, window by window
+  .compacted(size)        the live entries written again as a fresh database
 
 status: 0 OK, NOTFOUND, DELETED (Database::Get reports NotFound), MULTIPART
 (MultipartRequired), or the decoder's -1 / -2 (see get.py).  Databases opened
@@ -79,6 +83,7 @@ class HSTableIndex:
         self.fileid = np.array([int(f, 16) for f in self.names], np.uint32)
         self.files = DeviceBuffer(total + 64)
         self.h = None
+        self._scan = None                # (verify, live, key bytes, max key length) of the prepared scan
         st = stream.ptr if stream else None
         self.files.upload(buf, stream=st)
         h = ctypes.c_void_p()
@@ -193,6 +198,116 @@ class HSTableIndex:
             for b in (out, scratch):
                 if b is not None:
                     b.free()
+
+    # ------------------------------------------------------------------ scan
+    def scan_prepare(self, verify: int = 0, stream: Stream | None = None) -> int:
+        """The liveness pass and the ordered live list (kdb_index_scan_prepare):
+        the number of live entries.  Implicit on the first scan and repeated
+        when `verify` changes (the header CRC-8 is part of liveness)."""
+        live, kbytes, kmax = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+        self._scan = None
+        _lib.check(lib().kdb_index_scan_prepare(self.h, stream.ptr if stream else None, 1 if verify else 0,
+                                                ctypes.byref(live), ctypes.byref(kbytes), ctypes.byref(kmax)),
+                   "kdb_index_scan_prepare")
+        self._scan = (1 if verify else 0, live.value, kbytes.value, kmax.value)
+        return live.value
+
+    def _prepared(self, verify: int, stream: Stream | None) -> tuple[int, int, int]:
+        s = self._scan
+        if s is None or s[0] != (1 if verify else 0):
+            self.scan_prepare(verify, stream)
+        return self._scan[1:]
+
+    def scan_sort_steps(self) -> int:
+        """Compare-exchange passes the last scan_prepare ran (0: the files' rows ascend)."""
+        steps = ctypes.c_uint32(0)
+        _lib.check(lib().kdb_index_scan_sort_steps(self.h, ctypes.byref(steps)), "kdb_index_scan_sort_steps")
+        return steps.value
+
+    def run_scan(self, L: _Lookup, st, first: int, n: int, multipart_required: int = MULTIPART_REQUIRED) -> None:
+        """kdb_index_scan_batch into `L` (its keys buffer takes the packed keys)."""
+        _lib.check(lib().kdb_index_scan_batch(
+            self.h, st, first, n, multipart_required, L.scratch.ptr, L.scratch_bytes, L.keys.ptr, L.keys.nbytes,
+            L.p("key_off"), L.p("key_len"), L.p("stored_off"), L.p("avail"), L.p("svc"), L.p("size"),
+            L.p("checksum"), L.p("checksum_initial"), L.p("out_off"), L.p("location"), L.p("status"),
+            L.p("summary")), "kdb_index_scan_batch")
+
+    def scan(self, first: int = 0, count: int | None = None, verify: int = 0,
+             multipart_required: int = MULTIPART_REQUIRED, stream: Stream | None = None,
+             frame_cap: int | None = None) -> list[tuple[bytes, int, bytes]]:
+        """One window [first, first + count) of the live entries in iterator
+        order (files by (timestamp, fileid), offsets ascending):
+        [(key, status, value)], values decoded by kdb_get_values_batch.  status
+        is 0, MULTIPART (value b"") or the decoder's -1 / -2."""
+        live, _, kmax = self._prepared(verify, stream)
+        n = live - first if count is None else count
+        if first < 0 or n < 0 or first + n > live:
+            raise _lib.HipError(f"scan window [{first}, {first + n}) outside the {live} live entries")
+        if n == 0:
+            return []
+        st = stream.ptr if stream else None
+        L = _Lookup(n, n * kmax)
+        out = scratch = None
+        try:
+            self.run_scan(L, st, first, n, multipart_required)
+            found, out_bytes, frame_cap, max_in, max_out = self.decode_plan(L, st, n, frame_cap)
+            lo, hi = L.off["key_off"], L.off["key_off"] + 8 * n
+            koff = L.meta.download(hi - lo, lo, dtype=np.uint64, stream=st)
+            klen = L.meta.download(4 * n, L.off["key_len"], dtype=np.uint32, stream=st)
+            status = L.meta.download(4 * n, L.off["status"], dtype=np.int32, stream=st)
+            kbytes = int(koff[-1]) + int(klen[-1])
+            kdata = L.keys.download(kbytes, stream=st) if kbytes else np.zeros(0, np.uint8)
+            keys = [kdata[int(o):int(o) + int(m)].tobytes() for o, m in zip(koff, klen)]
+            if found == 0:
+                return [(k, int(s), b"") for k, s in zip(keys, status)]
+            out = DeviceBuffer(out_bytes + 64)
+            scratch = DeviceBuffer(int(lib().kdb_get_scratch_bytes(n, frame_cap)))
+            self.run_decode(L, st, n, verify, out, scratch, frame_cap, max_in, max_out)
+            ooff = L.meta.download(8 * n, L.off["out_off"], dtype=np.uint64, stream=st)
+            olen = L.meta.download(8 * n, L.off["out_len"], dtype=np.uint64, stream=st)
+            dstatus = L.meta.download(4 * n, L.off["dstatus"], dtype=np.int32, stream=st)
+            data = out.download(out_bytes, stream=st)
+            res = []
+            for i in range(n):
+                if status[i] != 0:
+                    res.append((keys[i], int(status[i]), b""))
+                else:
+                    res.append((keys[i], int(dstatus[i]), data[int(ooff[i]):int(ooff[i]) + int(olen[i])].tobytes()))
+            return res
+        finally:
+            L.free()
+            for b in (out, scratch):
+                if b is not None:
+                    b.free()
+
+    def items(self, batch: int = 65536, verify: int = 0, multipart_required: int = MULTIPART_REQUIRED,
+              stream: Stream | None = None):
+        """Generator over every live entry, a window of `batch` at a time, so a
+        large database never has all its values in memory at once."""
+        live, _, _ = self._prepared(verify, stream)
+        for first in range(0, live, max(batch, 1)):
+            yield from self.scan(first, min(batch, live - first), verify, multipart_required, stream)
+
+    def compacted(self, hstable_size: int = 32 << 20, batch: int = 65536, verify: int = 0) -> dict[str, bytes]:
+        """An offline compaction: the live entries (every key once, no deletes,
+        no overwritten entries) written again through put.write_hstables, a
+        window of the scan per write-buffer flush.  The files are an ordinary
+        database holding exactly the live entries; this does not claim the
+        file layout the reference's own compaction produces."""
+        from . import put
+        w = put.HSTableWriter(hstable_size, self.hash_type)
+        window = []
+        for key, status, value in self.items(batch, verify, multipart_required=1 << 62):
+            if status != 0:
+                raise _lib.HipError(f"compacted: value of {key!r} does not decode (status {status})")
+            window.append((key, value))
+            if len(window) == batch:
+                w.append(put.put_entries(window, self.hash_type))
+                window = []
+        if window:
+            w.append(put.put_entries(window, self.hash_type))
+        w.close()
+        return w.files()
 
     def close(self) -> None:
         if self.h:
