@@ -102,6 +102,17 @@ SIGNATURES = {
     "kdb_hstable_writer_save": (_i, [_vp, _c.c_char_p]),
     "kdb_hstable_writer_reset": (_i, [_vp]),
     "kdb_hstable_writer_destroy": (_i, [_vp]),
+    # include/kdb_hstable_dev.h (HSTable files built in device memory)
+    "kdb_hstable_dev_arena_bytes": (_u64, [_u64, _u64, _u64]),
+    "kdb_hstable_dev_create": (_i, [_u64, _u32, _u64, _c.POINTER(_vp)]),
+    "kdb_hstable_dev_destroy": (_i, [_vp]),
+    "kdb_hstable_dev_append": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32]),
+    "kdb_hstable_dev_close": (_i, [_vp]),
+    "kdb_hstable_dev_file_count": (_i, [_vp, _c.POINTER(_u32)]),
+    "kdb_hstable_dev_files": (_i, [_vp, _c.POINTER(_vp), _vp, _vp, _vp, _u32]),
+    "kdb_hstable_dev_download": (_i, [_vp, _u32, _vp, _vp]),
+    "kdb_hstable_dev_reset": (_i, [_vp]),
+    "kdb_hstable_dev_feed": (_i, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
     # link-time aliases of the reference's lz4.h names
     "LZ4_compressBound": (_i, [_i]),
     "LZ4_compress_limitedOutput": (_i, [_c.c_char_p, _vp, _i, _i]),

@@ -11,6 +11,10 @@ set of closed HSTable files and the batched lookup in front of the decoder.
                           (Database::NewIterator): [(key, status, value)]
   .items(batch)           a generator over all of them, window by window
   .compacted(size)        the live entries written again as a fresh database
+  .compacted_device(size) the same with no value byte leaving device memory
+  HSTableIndex.from_resident(writer)
+                          an index over the files a put.DeviceHSTableWriter
+                          holds in device memory, with no upload
 
 status: 0 OK, NOTFOUND, DELETED (Database::Get reports NotFound), MULTIPART
 (MultipartRequired), or the decoder's -1 / -2 (see get.py).  Databases opened
@@ -66,6 +70,16 @@ class _Lookup:
             b.free()
 
 
+class _Borrowed:
+    """A device range that belongs to someone else: free() leaves it alone."""
+
+    def __init__(self, ptr: int, nbytes: int):
+        self.ptr, self.nbytes = ptr, nbytes
+
+    def free(self) -> None:
+        pass
+
+
 class HSTableIndex:
     def __init__(self, files: dict[str, bytes], hash_type: int = 1, stream: Stream | None = None):
         self.names = sorted(files)
@@ -96,6 +110,37 @@ class HSTableIndex:
                    "kdb_index_load_files")
         self.file_status = {f: int(s) for f, s in zip(self.names, status[:n])}
         self.entries = entries.value
+
+    @classmethod
+    def from_resident(cls, writer, stream: Stream | None = None) -> "HSTableIndex":
+        """An index over the closed files of a put.DeviceHSTableWriter where
+        they lie in device memory: no download, no upload.  The index BORROWS
+        the writer's arena: close() of such an index frees the index alone,
+        and the writer must outlive it -- no reset() and no free() of the
+        writer while the index is in use (the index keeps a reference to the
+        writer, so it is not collected from under it)."""
+        ptr, off, size, fid = writer.resident()
+        self = cls.__new__(cls)
+        self.names = ["%08x" % int(f) for f in fid]
+        self.hash_type = writer.hash_type
+        self.file_off, self.file_size, self.fileid = off.copy(), size.copy(), fid.copy()
+        self.files = _Borrowed(ptr, writer.arena)
+        self._owner = writer
+        self.h = None
+        self._scan = None
+        n = len(fid)
+        st = stream.ptr if stream else None
+        h = ctypes.c_void_p()
+        _lib.check(lib().kdb_index_create(self.hash_type, ctypes.byref(h)), "kdb_index_create")
+        self.h = h.value
+        status = np.zeros(max(n, 1), np.int32)
+        entries = ctypes.c_uint64(0)
+        _lib.check(lib().kdb_index_load_files(self.h, st, ptr, self.file_off.ctypes.data, self.file_size.ctypes.data,
+                                              self.fileid.ctypes.data, n, status.ctypes.data, ctypes.byref(entries)),
+                   "kdb_index_load_files")
+        self.file_status = {f: int(s) for f, s in zip(self.names, status[:n])}
+        self.entries = entries.value
+        return self
 
     def pairs(self) -> tuple[np.ndarray, np.ndarray]:
         """The loaded rows in sequence order: (hashed keys, fileid << 32 | offset)."""
@@ -308,6 +353,98 @@ class HSTableIndex:
             w.append(put.put_entries(window, self.hash_type))
         w.close()
         return w.files()
+
+    def compacted_device(self, hstable_size: int = 32 << 20, batch: int = 65536, verify: int = 0):
+        """compacted() with no value byte leaving device memory: a closed
+        put.DeviceHSTableWriter holding, batch for batch, the files
+        compacted() returns (`.files()` downloads them, from_resident() opens
+        them in place).  Each scan window's decode outputs are the inputs of
+        kdb_put_entries_batch as they lie -- the packed keys, the decode buffer
+        with out_off / out_len as value_off / value_len -- and the entries go
+        to the device writer.  Per window the host sees the 40-byte summary,
+        one flag and the writer's plan."""
+        from . import put
+        batch = max(batch, 1)
+        live, kbytes, kmax = self._prepared(verify, None)
+        windows = [(first, min(batch, live - first)) for first in range(0, live, batch)]
+        big = 1 << 62
+        # sizing pass: the window summaries alone bound the entry bytes
+        bound = 0
+        for first, n in windows:
+            L = _Lookup(n, n * kmax)
+            try:
+                self.run_scan(L, None, first, n, big)
+                _, out_bytes, _, _, _ = self.decode_plan(L, None, n)
+            finally:
+                L.free()
+            bound += out_bytes + n * (72 + kmax) + (out_bytes // 65536 + n + 1) * 16 + 64
+        w = put.DeviceHSTableWriter(hstable_size, self.hash_type,
+                                    put.DeviceHSTableWriter.arena_bytes(hstable_size, bound, live))
+        try:
+            for first, n in windows:
+                self._compact_window(w, first, n, kmax, verify, big)
+            w.close()
+        except Exception:
+            w.free()
+            raise
+        return w
+
+    def _compact_window(self, w, first: int, n: int, kmax: int, verify: int, big: int) -> None:
+        from . import put
+        L = _Lookup(n, n * kmax)
+        bufs = [L]
+        try:
+            self.run_scan(L, None, first, n, big)
+            found, out_bytes, frame_cap, max_in, max_out = self.decode_plan(L, None, n)
+            if found != n:
+                self._compact_fail(L, n, False)
+            out = DeviceBuffer(out_bytes + 64)
+            bufs.append(out)
+            scratch = DeviceBuffer(int(lib().kdb_get_scratch_bytes(n, frame_cap)))
+            bufs.append(scratch)
+            self.run_decode(L, None, n, verify, out, scratch, frame_cap, max_in, max_out)
+            # part_first u32 (n + 1), chunk_len u32 (n), flag u32
+            feed = DeviceBuffer(_a8(4 * (n + 1)) + _a8(4 * n) + 8)
+            bufs.append(feed)
+            part_first, chunk_len = feed.ptr, feed.ptr + _a8(4 * (n + 1))
+            flag = chunk_len + _a8(4 * n)
+            _lib.check(lib().kdb_hstable_dev_feed(None, L.p("out_len"), L.p("status"), L.p("dstatus"), n, part_first,
+                                                  chunk_len, flag), "kdb_hstable_dev_feed")
+            raw = max(out_bytes, 1)
+            pscratch_bytes = int(lib().kdb_put_scratch_bytes(n, n, raw))
+            pscratch = DeviceBuffer(pscratch_bytes)
+            bufs.append(pscratch)
+            entries = DeviceBuffer(raw + n * (72 + kmax) + (raw // 65536 + n + 1) * 16 + 64)
+            bufs.append(entries)
+            po = DeviceBuffer(n * 32 + 64)
+            bufs.append(po)
+            o = po.ptr
+            e_off, e_len, hashed, crc, kind, status, total = (o, o + 8 * n, o + 12 * n, o + 20 * n, o + 24 * n,
+                                                              o + 28 * n, o + 32 * n)
+            _lib.check(lib().kdb_put_entries_batch(
+                None, L.keys.ptr, L.p("key_off"), L.p("key_len"), out.ptr, L.p("out_off"), L.p("out_len"), part_first,
+                chunk_len, n, max_out, n, self.hash_type, pscratch.ptr, pscratch_bytes, raw, entries.ptr, e_off,
+                e_len, total, hashed, crc, kind, status), "kdb_put_entries_batch")
+            if int(feed.download(4, flag - feed.ptr, dtype=np.uint32)[0]):
+                self._compact_fail(L, n, True)
+            w.append_ptrs(None, entries.ptr, e_off, e_len, hashed, kind, status, n)
+            _lib.check(lib().kdb_lz4_stream_sync(None), "sync")     # the window's buffers are read by queued work
+        finally:
+            for b in bufs:
+                b.free()
+
+    def _compact_fail(self, L: _Lookup, n: int, decoded: bool) -> None:
+        """The error compacted() raises, for the window's first value that does not decode."""
+        status = L.meta.download(4 * n, L.off["status"], dtype=np.int32)
+        dstatus = L.meta.download(4 * n, L.off["dstatus"], dtype=np.int32) if decoded else status
+        koff = L.meta.download(8 * n, L.off["key_off"], dtype=np.uint64)
+        klen = L.meta.download(4 * n, L.off["key_len"], dtype=np.uint32)
+        for i in range(n):
+            s = int(status[i]) or int(dstatus[i])
+            if s:
+                key = L.keys.download(int(klen[i]), int(koff[i])).tobytes() if klen[i] else b""
+                raise _lib.HipError(f"compacted: value of {key!r} does not decode (status {s})")
+        raise _lib.HipError("compacted: a value of the window does not decode")
 
     def close(self) -> None:
         if self.h:

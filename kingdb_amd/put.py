@@ -9,6 +9,9 @@ framing on the host (csrc/hstable.cc).
   put_entries(puts)          one GPU batch: entry bytes, key hashes, CRCs
   HSTableWriter              the HSTable files those entries make
   write_hstables(puts, ...)  both, batch by batch: {file name: bytes}
+  DeviceHSTableWriter        the same files framed on the GPU, in device memory
+                             (csrc/hstable_dev.hip, include/kdb_hstable_dev.h)
+  write_hstables_device(...) write_hstables with both stages on the device
 
 A put is (key, value) or (key, value, chunks): `chunks` lists the sizes of
 the PutPart calls the value arrives in (default: one call, i.e. Database::Put
@@ -247,3 +250,137 @@ def write_hstables(puts, hstable_size: int = 32 << 20, hash_type: int = 1, batch
         w.append(put_entries(puts[i:i + step], hash_type))
     w.close()
     return w.files()
+
+
+def put_entries_device(puts, hash_type: int = 1, stream: Stream | None = None) -> tuple[PutBatch, int]:
+    """put_entries() that leaves its outputs where they are: (the PutBatch
+    holding them in device memory, n).  The caller frees the batch."""
+    kbuf, vbuf, koff, klen, voff, vlen, pf, clen = _layout(puts)
+    n = len(puts)
+    nparts = len(clen)
+    raw = int(vlen.sum()) if n else 0
+    b = PutBatch(max(n, 1), max(nparts, 1), max(raw, 1), max(len(kbuf), 1))
+    try:
+        st = stream.ptr if stream else None
+        if len(kbuf):
+            b.keys.upload(kbuf, stream=st)
+        if len(vbuf):
+            b.values.upload(vbuf, stream=st)
+        # laid out for the capacity, as run_device reads it (n = 0: one empty slot)
+        c = b.n
+        meta = np.zeros(c * 32 + 8, np.uint8)
+        for arr, at in ((koff, 0), (klen, 8 * c), (voff, 12 * c), (vlen, 20 * c), (pf, 28 * c)):
+            a = arr.view(np.uint8)
+            meta[at:at + len(a)] = a
+        b.vmeta.upload(meta, stream=st)
+        if nparts:
+            b.chunks.upload(clen, stream=st)
+        b.run_device(stream, n, nparts, int(clen.max()) if nparts else 0, raw, hash_type)
+    except Exception:
+        b.free()
+        raise
+    return b, n
+
+
+def entries_bound(puts) -> int:
+    """An upper bound on the entry bytes `puts` make (PutBatch's own sizing)."""
+    raw = sum(len(p[1]) for p in puts)
+    return raw + sum(len(p[0]) for p in puts) + len(puts) * 72 + (raw // 65536 + len(puts) + 1) * 16 + 64
+
+
+class DeviceHSTableWriter:
+    """HSTable files for one database directory, built in device memory
+    (include/kdb_hstable_dev.h): the files of HSTableWriter, byte for byte,
+    with the cut, the offset arrays, the header blocks and the footers written
+    by kernels.  `arena_bytes` is the one device buffer the files live in
+    (arena_bytes() bounds what a database needs; the default holds 256 MiB of
+    entries in 2 Mi puts).  An append that does not fit raises HipError and
+    leaves the writer as it was."""
+
+    def __init__(self, hstable_size: int = 32 << 20, hash_type: int = 1, arena_bytes: int | None = None):
+        if arena_bytes is None:
+            arena_bytes = self.arena_bytes(hstable_size, 256 << 20, 2 << 20)
+        h = ctypes.c_void_p()
+        _lib.check(lib().kdb_hstable_dev_create(hstable_size, hash_type, arena_bytes, ctypes.byref(h)),
+                   "hstable_dev_create")
+        self.h = h.value
+        self.hstable_size, self.hash_type, self.arena = hstable_size, hash_type, arena_bytes
+
+    @staticmethod
+    def arena_bytes(hstable_size: int, entry_bytes: int, n_entries: int) -> int:
+        return int(lib().kdb_hstable_dev_arena_bytes(hstable_size, entry_bytes, n_entries))
+
+    def append_ptrs(self, stream_ptr, d_entries: int, d_entry_off: int, d_entry_len: int, d_hashed: int,
+                    d_kind: int, d_status: int, n: int) -> None:
+        """One batch from raw device pointers (the outputs of kdb_put_entries_batch)."""
+        _lib.check(lib().kdb_hstable_dev_append(self.h, stream_ptr, d_entries, d_entry_off, d_entry_len, d_hashed,
+                                                d_kind, d_status, n), "hstable_dev_append")
+
+    def append_batch(self, b: PutBatch, n: int, stream: Stream | None = None) -> None:
+        """One batch from the device outputs of PutBatch.run_device(…, n, …), as they lie."""
+        o = b._optr(n)
+        self.append_ptrs(stream.ptr if stream else None, b.entries.ptr, o["entry_off"], o["entry_len"], o["hashed"],
+                         o["kind"], o["status"], n)
+
+    def close(self) -> None:
+        _lib.check(lib().kdb_hstable_dev_close(self.h), "hstable_dev_close")
+
+    def reset(self) -> None:
+        """A fresh directory; the arena is kept."""
+        _lib.check(lib().kdb_hstable_dev_reset(self.h), "hstable_dev_reset")
+
+    def resident(self) -> tuple[int, np.ndarray, np.ndarray, np.ndarray]:
+        """The closed files where they are: (device pointer of the arena,
+        file_off, file_size, fileid), the arguments of kdb_index_load_files."""
+        c = ctypes.c_uint32(0)
+        _lib.check(lib().kdb_hstable_dev_file_count(self.h, ctypes.byref(c)), "hstable_dev_file_count")
+        n = c.value
+        off, size, fid = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint32)
+        base = ctypes.c_void_p()
+        _lib.check(lib().kdb_hstable_dev_files(self.h, ctypes.byref(base), off.ctypes.data, size.ctypes.data,
+                                               fid.ctypes.data, n), "hstable_dev_files")
+        return base.value or 0, off[:n], size[:n], fid[:n]
+
+    def files(self, stream: Stream | None = None) -> dict[str, bytes]:
+        """{file name: bytes} of the closed files, downloaded."""
+        _, _, size, fid = self.resident()
+        out = {}
+        for i in range(len(fid)):
+            buf = np.empty(max(int(size[i]), 1), np.uint8)
+            _lib.check(lib().kdb_hstable_dev_download(self.h, i, buf.ctypes.data, stream.ptr if stream else None),
+                       "hstable_dev_download")
+            out["%08x" % int(fid[i])] = buf[:int(size[i])].tobytes()
+        return out
+
+    def free(self) -> None:
+        if self.h:
+            lib().kdb_hstable_dev_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def write_hstables_device(puts, hstable_size: int = 32 << 20, hash_type: int = 1, batch: int | None = None
+                          ) -> dict[str, bytes]:
+    """write_hstables() with both stages on the device: the entries never
+    leave it, only the finished files come back."""
+    step = batch or max(len(puts), 1)
+    bound = sum(entries_bound(puts[i:i + step]) for i in range(0, len(puts), step))
+    w = DeviceHSTableWriter(hstable_size, hash_type,
+                            DeviceHSTableWriter.arena_bytes(hstable_size, bound, len(puts)))
+    try:
+        for i in range(0, len(puts), step):
+            b, n = put_entries_device(puts[i:i + step], hash_type)
+            try:
+                w.append_batch(b, n)
+                _lib.check(lib().kdb_lz4_stream_sync(None), "sync")     # the batch's buffers are read by queued work
+            finally:
+                b.free()
+        w.close()
+        return w.files()
+    finally:
+        w.free()
