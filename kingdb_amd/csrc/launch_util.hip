@@ -96,6 +96,120 @@ hipError_t work_counter_release(hipStream_t st, uint32_t* ctr) {
   return hipSuccess;
 }
 
+// ---------------------------------------------------------------------------
+// The emission helpers' scratch (lz4_device.h: EmitScratch).  kEmitSets sets
+// per device, handed out round-robin; a set's event is recorded on the stream
+// of its last launch and waited for before the set goes out again, so two
+// launches in flight never share rings.  The words are zeroed once, when the
+// pool is made: every launch has a generation of its own (never 0), and a word
+// of another generation reads as "nothing published".
+#ifndef KDB_LZ4_EMIT_HELPERS_DEFAULT
+#define KDB_LZ4_EMIT_HELPERS_DEFAULT 1
+#endif
+#ifndef KDB_LZ4_EMIT_RING_DEFAULT
+#define KDB_LZ4_EMIT_RING_DEFAULT 4   // (with five helpers: 7.31 ms against 7.35 at depth 2)
+#endif
+namespace {
+constexpr uint32_t kEmitSets = 8;
+struct EmitPool {
+  uint8_t* base = nullptr;
+  uint32_t waves = 0, ring_bytes = 0;      // parse waves a set holds; ring bytes per wave
+  size_t set_bytes = 0, ctl_bytes = 0;
+  uint64_t ticks_per_s = 100000000ull;
+  std::atomic<uint32_t> next{0}, gen{0};
+  hipEvent_t ev[kEmitSets] = {};
+  // 0: free; 1: taken, its launch not queued yet; 2: its event recorded behind the launch
+  int state[kEmitSets] = {};
+  std::mutex mu;               // guards ev/state
+};
+std::unordered_map<int, EmitPool*> g_emit_pools;
+
+long env_long(const char* name, long dflt) {
+  const char* e = getenv(name);
+  return e && *e ? strtol(e, nullptr, 0) : dflt;
+}
+}  // namespace
+
+hipError_t emit_scratch(hipStream_t st, uint32_t parse_waves, uint32_t ring_bytes, EmitScratch* es) {
+  (void)st;
+  *es = EmitScratch();
+  if (env_long("KDB_LZ4_EMIT_HELPERS", KDB_LZ4_EMIT_HELPERS_DEFAULT) == 0) return hipSuccess;
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  EmitPool* p;
+  {
+    std::lock_guard<std::mutex> l(g_mu);
+    EmitPool*& slot = g_emit_pools[dev];
+    if (!slot) {
+      int cus = 0, khz = 0;
+      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+      EmitPool* np = new EmitPool();
+      np->waves = (uint32_t)cus * 10u;     // one ten-wave workgroup per CU
+      np->ring_bytes = ring_bytes;
+      np->ctl_bytes = ((size_t)np->waves * 16u + 255u) & ~(size_t)255u;
+      np->set_bytes = np->ctl_bytes + (size_t)np->waves * ring_bytes;
+      if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) == hipSuccess && khz > 0)
+        np->ticks_per_s = (uint64_t)khz * 1000ull;
+      e = hipMalloc(&np->base, kEmitSets * np->set_bytes);
+      if (e == hipSuccess) e = hipMemset(np->base, 0, kEmitSets * np->set_bytes);
+      if (e != hipSuccess) {
+        if (np->base) (void)hipFree(np->base);
+        delete np;
+        return e;
+      }
+      slot = np;
+    }
+    p = slot;
+  }
+  if (parse_waves > p->waves || ring_bytes != p->ring_bytes) return hipSuccess;   // no set holds it: helpers off
+  // round-robin over the sets no other host thread holds right now; a set
+  // whose last launch may still run is waited for (with eight sets that launch
+  // is eight launches back); all held: this launch runs without helpers
+  uint32_t i = kEmitSets;
+  {
+    std::lock_guard<std::mutex> l(p->mu);
+    const uint32_t first = p->next.fetch_add(1);
+    for (uint32_t k = 0; k < kEmitSets && i == kEmitSets; ++k)
+      if (p->state[(first + k) % kEmitSets] != 1) i = (first + k) % kEmitSets;
+    if (i == kEmitSets) return hipSuccess;
+    if (p->state[i] == 2 && (e = hipEventSynchronize(p->ev[i])) != hipSuccess) return e;
+    p->state[i] = 1;
+  }
+  uint32_t g = p->gen.fetch_add(1) + 1u;
+  if (g == 0) g = p->gen.fetch_add(1) + 1u;
+  const long d = env_long("KDB_LZ4_EMIT_RING", KDB_LZ4_EMIT_RING_DEFAULT);
+  uint8_t* set = p->base + (size_t)i * p->set_bytes;
+  es->ctl = reinterpret_cast<uint64_t*>(set);
+  es->ring = set + p->ctl_bytes;
+  es->depth = d >= 4 ? 4u : d >= 2 ? 2u : 1u;
+  if ((size_t)es->depth * 576u > ring_bytes) es->depth = 1u;
+  es->gen = g;
+  es->cap_ticks = 10ull * p->ticks_per_s;   // 10 s: far beyond any launch, short of a stuck machine
+  es->set = (int)i;
+  return hipSuccess;
+}
+
+hipError_t emit_scratch_release(hipStream_t st, const EmitScratch& es) {
+  if (es.set < 0) return hipSuccess;
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  EmitPool* p;
+  {
+    std::lock_guard<std::mutex> l(g_mu);
+    p = g_emit_pools[dev];
+  }
+  if (!p) return hipErrorInvalidValue;
+  std::lock_guard<std::mutex> l(p->mu);
+  const int i = es.set;
+  p->state[i] = 0;
+  if (!p->ev[i] && (e = hipEventCreateWithFlags(&p->ev[i], hipEventDisableTiming)) != hipSuccess) return e;
+  if ((e = hipEventRecord(p->ev[i], st)) != hipSuccess) return e;
+  p->state[i] = 2;
+  return hipSuccess;
+}
+
 long kdb_tune(const char* name, long dflt) {
 #ifdef KDB_LZ4_TUNING
   const char* e = getenv(name);
@@ -119,9 +233,10 @@ uint32_t services_resident(int dev);   // kdb_lz4_capi.hip (service.h)
 // workgroup that is admitted late simply takes fewer values).
 // `waves` > 1: workgroups of that many waves (one value each at a time), at
 // most ceil(n / waves) of them.
-uint32_t persistent_grid(const void* kern, size_t lds, uint32_t n, uint32_t waves) {
+uint32_t persistent_grid(const void* kern, size_t lds, uint32_t n, uint32_t waves, uint32_t helpers) {
   int per_cu = 0, dev = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * (int)waves, lds) != hipSuccess || per_cu < 1)
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * (int)(waves + helpers), lds) != hipSuccess ||
+      per_cu < 1)
     per_cu = 1;
   (void)hipGetDevice(&dev);
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)

@@ -597,14 +597,269 @@ __device__ __forceinline__ uint32_t wave_incl_sum(uint32_t x) {
   return x;
 }
 
+// The batched emission (compress_block's kBatch): encodes the nseq <= 64
+// sequences recorded in rlm / roff (lane k: sequence k, lit | ml << 16 and the
+// offset) at block position op, their literals starting at value position
+// banchor and read through src -- LDS for the wave that parsed the value,
+// global memory for an emission helper wave.  Returns the block position
+// after them.  (lz4.cc:535-592: the same bytes.)
+template <class Src>
+__device__ __forceinline__ uint32_t flush_seqs(const Src& src, const __amdgpu_buffer_rsrc_t out_rsrc, uint32_t rlm,
+                                               uint32_t roff, uint32_t nseq, uint32_t banchor, uint32_t op) {
+  const uint32_t lane = lane_id();
+  const bool on = lane < nseq;
+  const uint32_t L = on ? (rlm & 0xffffu) : 0u, M = on ? (rlm >> 16) : 0u;
+  const uint32_t nl1 = run_bytes(L), nm1 = run_bytes(M);
+  // encoded bytes | input bytes << 16 (each total < 2^16: S <= 8 KiB here)
+  const uint32_t x = on ? (L + nl1 + nm1 + 3u) | ((L + kMinMatch + M) << 16) : 0u;
+  const uint32_t xi = wave_incl_sum(x);
+  const uint32_t ex = xi - x;
+  const uint32_t o = op + (ex & 0xffffu);              // the token
+  const uint32_t a = banchor + (ex >> 16);             // the literals in the value
+  const uint32_t lp = o + 1u + nl1;                    // the literals in the block
+  const uint32_t po = lp + L;                          // the offset (LE16)
+  auto st8 = [&](uint32_t v, bool w, uint32_t pos) {
+    __builtin_amdgcn_raw_buffer_store_b8((uint8_t)v, out_rsrc, w ? (int)pos : (int)0x80000000, 0, 0);
+  };
+  st8((min(L, kRunMask) << 4) | min(M, kMlMask), on, o);
+  st8(roff, on, po);
+  st8(roff >> 8, on, po + 1u);
+  // the length runs: 255s, then run_last (lz4.cc:539-545, 582-590)
+#pragma unroll 1
+  for (uint32_t j = 0; ballot(j < max(nl1, nm1)) != 0; ++j) {
+    st8(j + 1u == nl1 ? run_last(L, nl1) : 255u, j < nl1, o + 1u + j);
+    st8(j + 1u == nm1 ? run_last(M, nm1) : 255u, j < nm1, po + 2u + j);
+  }
+  // the literals: one wave-wide byte store per sequence (its first 64),
+  // in passes of G sequences with their reads issued together (eight
+  // while eight are left, then two: a sequence past nseq has L = 0 and
+  // stores nothing); the block position goes in the store's scalar
+  // offset.  Positions < 2^16: packed.
+  const uint32_t la = lp | (a << 16);
+  auto lit_pass = [&](uint32_t s0, auto g_c) {
+    constexpr uint32_t G = decltype(g_c)::value;
+    uint32_t b[G], vo[G], so[G];
+#pragma unroll
+    for (uint32_t k = 0; k < G; ++k) {
+      const uint32_t Ls = readlane(L, s0 + k), pk = readlane(la, s0 + k);
+      b[k] = src.u8((pk >> 16) + lane);
+      vo[k] = lane < Ls ? lane : 0x80000000u;
+      so[k] = pk & 0xffffu;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < G; ++k)
+      __builtin_amdgcn_raw_buffer_store_b8((uint8_t)b[k], out_rsrc, (int)vo[k], (int)so[k], 0);
+  };
+  uint32_t s0 = 0;
+#pragma unroll 1
+  for (; s0 + 8u <= nseq; s0 += 8u) lit_pass(s0, std::integral_constant<uint32_t, 8>{});
+#pragma unroll 1
+  for (; s0 < nseq; s0 += 2u) lit_pass(s0, std::integral_constant<uint32_t, 2>{});   // s0 + 1 <= 63
+  // literal runs longer than 64 bytes (rare): the rest, sequence by sequence
+  for (uint64_t lng = ballot(L > 64u); lng; lng &= lng - 1u) {
+    const uint32_t s = (uint32_t)__builtin_ctzll(lng);
+    const uint32_t Ls = readlane(L, s), pk = readlane(la, s);
+#pragma unroll 1
+    for (uint32_t j = 64u; j < Ls; j += 64u)
+      st8(src.u8((pk >> 16) + j + lane), j + lane < Ls, (pk & 0xffffu) + j + lane);
+  }
+  return op + (readlane(xi, 63) & 0xffffu);
+}
+
+// ------------------------------------------------------ emission helper waves
+//
+// The <= 4 KiB batched kernel runs kHelpers extra waves per workgroup that use
+// no LDS (lz4_compress_kernel).  A parse wave whose value ended as ONE batch
+// (no flush yet: at most 64 sequences) hands the emission over instead of
+// doing it while it holds its 16 KiB: it writes the recorded sequences and a
+// header to a slot of its ring in global scratch and goes on to its next
+// value; a helper wave of the same workgroup encodes the block from the slot
+// and the value's bytes in global memory (in L2: the parse wave loaded them a
+// value ago), applies the raw fallback and writes the frame header, frame_len
+// and the status.  Every frame has one writer wave.
+//
+// Per parse wave two 64-bit words, generation << 32 | count: `pub`, the slots
+// it has published (bit 31: the wave has left its value loop), written by the
+// parse wave only, and `con`, the slots consumed, written by its helper only.
+// A word of another generation (an earlier launch's) reads as count 0, so the
+// words are never reset.  Both waves run on one CU: workgroup scope.
+//
+// A slot is published one hand-off late -- at the wave's next value end, or at
+// its exit -- when its stores were issued a value ago: the release costs the
+// parse wave no wait for them.  The parse wave never waits: with its ring full
+// (slots written and not yet consumed == depth) it emits the value itself.
+// A helper leaves when its parse waves have all left and their rings are
+// empty, or after cap_ticks of the wall clock: the sentinel status
+// (kUnsupported) its unconsumed slots keep then fails the launch visibly.
+constexpr uint32_t kHandSlotBytes = 576u;   // rlm[64], roff[64], {value, S, anchor, nseq}, padded to 64 B
+constexpr uint32_t kHandMaxRing = 4u;       // slots allocated per parse wave (the depth is a launch parameter)
+constexpr uint32_t kHandDone = 0x80000000u;
+struct EmitHelp {
+  uint8_t* ring;        // nullptr: helpers off, every value emitted by its parse wave
+  uint64_t* ctl;        // {pub, con} per parse wave
+  uint32_t depth, gen;  // depth: 1, 2 or 4
+  uint64_t cap_ticks;
+};
+__device__ __forceinline__ uint32_t hand_count(uint64_t w, uint32_t gen) {
+  return (uint32_t)(w >> 32) == gen ? (uint32_t)w : 0u;
+}
+struct NoHand {
+  static constexpr bool kOn = false;
+};
+// a parse wave's end of the hand-off
+struct EmitHand {
+  static constexpr bool kOn = true;
+  uint8_t* ring;        // this wave's slots (nullptr: off)
+  uint64_t* ctl;        // this wave's {pub, con}
+  uint32_t depth, gen;  // depth: a power of two
+  uint32_t nput, npub;  // slots written; slots published
+  uint32_t v;           // the value being compressed
+  int32_t* ret;
+  uint64_t con_early;   // `con` as read when the value's parse began (peek)
+  // `con` only grows, so an early read can only understate the room: its load
+  // goes out before the parse, and push() reads again only when that says full
+  __device__ __forceinline__ void peek() {
+    if (ring) con_early = __hip_atomic_load(ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+  __device__ __forceinline__ void publish(uint32_t flag) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    if (lane_id() == 0)
+      __hip_atomic_store(ctl, ((uint64_t)gen << 32) | nput | flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    npub = nput;
+  }
+  // the value's one batch handed to the helper; false: the ring is full (or off)
+  __device__ __forceinline__ bool push(uint32_t rlm, uint32_t roff, uint32_t S, uint32_t anchor, uint32_t nseq) {
+    if (!ring) return false;
+    if (npub != nput) publish(0u);     // the previous hand-off: its stores went out a value ago
+    uint32_t con = uni(hand_count(con_early, gen));
+    if (nput - con >= depth) {
+      con = uni(hand_count(__hip_atomic_load(ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP), gen));
+      if (nput - con >= depth) return false;
+    }
+    // (the helper read the slot's last contents before it advanced `con`)
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    uint32_t* s = reinterpret_cast<uint32_t*>(ring + (size_t)(nput & (depth - 1u)) * kHandSlotBytes);
+    const uint32_t lane = lane_id();
+    s[lane] = rlm;
+    s[64u + lane] = roff;
+    if (lane == 0) {
+      reinterpret_cast<uint4*>(s + 128)[0] = make_uint4(v, S, anchor, nseq);
+      ret[v] = kUnsupported;           // until the helper writes the status
+    }
+    ++nput;
+    return true;
+  }
+  // the wave has left its value loop
+  __device__ __forceinline__ void finish() {
+    if (ring) publish(kHandDone);
+  }
+};
+
+// Value bytes in global memory for an emission helper: single byte loads,
+// 0 outside the value (flush_seqs reads up to 63 bytes past a literal run,
+// emit_seq clamps for LDS only).
+struct GlobalBytes {
+  const uint8_t* g;
+  uint32_t S;
+  __device__ __forceinline__ uint32_t u8(uint32_t i) const { return i < S ? (uint32_t)g[i] : 0u; }
+};
+
+// Helper wave h of a workgroup: serves the parse waves w with w % kHelpers == h
+// (lane w holds wave w's state).
+template <bool kFrame, uint32_t kWaves, uint32_t kHelpers>
+__device__ __forceinline__ void emit_helper_loop(uint32_t h, const EmitHelp& eh, const uint8_t* __restrict__ src,
+                                                 const uint64_t* __restrict__ src_off, uint32_t n, uint32_t in_cap,
+                                                 uint8_t* __restrict__ dst, const uint64_t* __restrict__ dst_off,
+                                                 uint32_t* __restrict__ frame_len, int32_t* __restrict__ ret) {
+  const uint32_t lane = lane_id();
+  const bool mine = lane < kWaves && lane % kHelpers == h;
+  const uint32_t gw0 = blockIdx.x * kWaves;
+  uint64_t* const myctl = eh.ctl + 2u * (size_t)(gw0 + (mine ? lane : 0u));
+  uint32_t ncon = 0;
+  const uint64_t t0 = wall_clock64();
+#pragma unroll 1
+  for (;;) {
+    uint64_t p = 0;
+    if (mine) p = __hip_atomic_load(myctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    const uint32_t c = hand_count(p, eh.gen);
+    uint64_t work = ballot(mine && (c & ~kHandDone) != ncon);
+    if (!work) {
+      if (ballot(mine && !(c & kHandDone)) == 0) break;          // all left, all rings empty
+      if (wall_clock64() - t0 > eh.cap_ticks) break;
+      __builtin_amdgcn_s_sleep(8);
+      continue;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#pragma unroll 1
+    for (; work; work &= work - 1ull) {
+      const uint32_t w = (uint32_t)__builtin_ctzll(work);
+      const uint32_t k = readlane(ncon, w);
+      const uint32_t* s = reinterpret_cast<const uint32_t*>(
+          eh.ring + ((size_t)(gw0 + w) * kHandMaxRing + (k & (eh.depth - 1u))) * kHandSlotBytes);
+      const uint32_t rlm = __hip_atomic_load(s + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      const uint32_t roff = __hip_atomic_load(s + 64u + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      const uint32_t hd = lane < 4u ? __hip_atomic_load(s + 128u + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+                                    : 0u;
+      const uint32_t v = readlane(hd, 0), S = readlane(hd, 1), anchor = readlane(hd, 2), nseq = readlane(hd, 3);
+      // the slot is read: the parse wave may write it again
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (lane == w) {
+        ++ncon;
+        __hip_atomic_store(myctl + 1, ((uint64_t)eh.gen << 32) | ncon, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+      // (a slot that cannot be one of this launch's is left alone: its status stays the sentinel)
+      if (v >= n || S > in_cap || anchor > S || nseq > 64u) continue;
+      const uint8_t* g = src + sload(src_off, v);
+      uint8_t* o = dst + sload(dst_off, v);
+      uint8_t* blk = kFrame ? o + 8 : o;
+      const GlobalBytes gs{g, S};
+      const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(blk, 0, 0x7fffffff, 0x00020000);
+      uint32_t op = nseq ? flush_seqs(gs, out_rsrc, rlm, roff, nseq, 0u, 0u) : 0u;
+      {  // the last literals (lz4.cc:625-637)
+        const uint32_t run = S - anchor, nl1 = run_bytes(run);
+        op += (uint32_t)emit_seq<false>(blk, 0, (int)op, min(run, kRunMask) << 4, run, nl1, run_last(run, nl1), gs, S,
+                                        anchor, false, 0u, 0u, 0u);
+      }
+      op = uni(op);
+      if (!kFrame) {
+        if (lane == 0) ret[v] = (int32_t)op;
+      } else {
+        const bool raw = op > S;                 // raw fallback (compressor.cc:40-48)
+        const uint32_t stored = raw ? 0u : op + 8u;
+        if (raw) {
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // block stores land before the raw bytes
+#pragma unroll 1
+          for (uint32_t i = lane; i < S; i += 256u) {        // 4 loads in flight per lane
+            uint8_t b[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) b[q] = i + 64u * q < S ? g[i + 64u * q] : 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) if (i + 64u * q < S) o[8u + i + 64u * q] = b[q];
+          }
+        }
+        if (lane < 8u) {                         // compressor.cc:53-54
+          const uint32_t wd = lane < 4u ? stored : S;
+          o[lane] = (uint8_t)(wd >> (8u * (lane & 3u)));
+        }
+        if (lane == 0) { ret[v] = 0; frame_len[v] = raw ? S + 8u : stored; }
+      }
+    }
+  }
+}
+
 
 // LZ4_compress_generic (byU16, limitedOutput).  `in` = LDS, value byte i at
 // in[i], i < S (every read is clamped into [0, S)).  Returns the block size
 // or 0 (limitedOutput failure, checked against `cap` at the reference's check
 // points), like the reference.
-template <bool kWide, bool kGuard, bool kBatchE = false, bool kLdsOut = false, class Src, class Tab>
+// hand (EmitHand, batched form only): a value that ends as one batch is handed
+// to an emission helper wave; the return value is then kUnsupported and the
+// helper writes the block, the frame around it and the status.
+template <bool kWide, bool kGuard, bool kBatchE = false, bool kLdsOut = false, class Src, class Tab,
+          class Hand = NoHand>
 __device__ __forceinline__ int compress_block(Src& src, uint32_t S, const Tab& tab,
-                                              uint8_t* __restrict__ out, int out_cap, int cap) {
+                                              uint8_t* __restrict__ out, int out_cap, int cap,
+                                              Hand* hand = nullptr) {
   const uint32_t lane = lane_id();
   int op = 0;
   uint32_t anchor = 0;
@@ -704,63 +959,11 @@ __device__ __forceinline__ int compress_block(Src& src, uint32_t S, const Tab& t
     uint32_t rlm = 0, roff = 0;       // lane k: sequence k of the batch (lit | ml << 16, offset)
     uint32_t nseq = 0, banchor = 0;   // sequences recorded; the batch's first anchor
     auto flush_batch = [&]() {
-      const bool on = lane < nseq;
-      const uint32_t L = on ? (rlm & 0xffffu) : 0u, M = on ? (rlm >> 16) : 0u;
-      const uint32_t nl1 = run_bytes(L), nm1 = run_bytes(M);
-      // encoded bytes | input bytes << 16 (each total < 2^16: S <= 8 KiB here)
-      const uint32_t x = on ? (L + nl1 + nm1 + 3u) | ((L + kMinMatch + M) << 16) : 0u;
-      const uint32_t xi = wave_incl_sum(x);
-      const uint32_t ex = xi - x;
-      const uint32_t o = (uint32_t)op + (ex & 0xffffu);   // the token
-      const uint32_t a = banchor + (ex >> 16);             // the literals in the value
-      const uint32_t lp = o + 1u + nl1;                    // the literals in the block
-      const uint32_t po = lp + L;                          // the offset (LE16)
-      auto st8 = [&](uint32_t v, bool w, uint32_t pos) {
-        __builtin_amdgcn_raw_buffer_store_b8((uint8_t)v, out_rsrc, w ? (int)pos : (int)0x80000000, 0, 0);
-      };
-      st8((min(L, kRunMask) << 4) | min(M, kMlMask), on, o);
-      st8(roff, on, po);
-      st8(roff >> 8, on, po + 1u);
-      // the length runs: 255s, then run_last (lz4.cc:539-545, 582-590)
-#pragma unroll 1
-      for (uint32_t j = 0; ballot(j < max(nl1, nm1)) != 0; ++j) {
-        st8(j + 1u == nl1 ? run_last(L, nl1) : 255u, j < nl1, o + 1u + j);
-        st8(j + 1u == nm1 ? run_last(M, nm1) : 255u, j < nm1, po + 2u + j);
-      }
-      // the literals: one wave-wide byte store per sequence (its first 64),
-      // in passes of G sequences with their LDS reads issued together (eight
-      // while eight are left, then two: a sequence past nseq has L = 0 and
-      // stores nothing); the block position goes in the store's scalar
-      // offset.  Positions < 2^16: packed.
-      const uint32_t la = lp | (a << 16);
-      auto lit_pass = [&](uint32_t s0, auto g_c) {
-        constexpr uint32_t G = decltype(g_c)::value;
-        uint32_t b[G], vo[G], so[G];
-#pragma unroll
-        for (uint32_t k = 0; k < G; ++k) {
-          const uint32_t Ls = readlane(L, s0 + k), pk = readlane(la, s0 + k);
-          b[k] = src.u8((pk >> 16) + lane);
-          vo[k] = lane < Ls ? lane : 0x80000000u;
-          so[k] = pk & 0xffffu;
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < G; ++k)
-          __builtin_amdgcn_raw_buffer_store_b8((uint8_t)b[k], out_rsrc, (int)vo[k], (int)so[k], 0);
-      };
-      uint32_t s0 = 0;
-#pragma unroll 1
-      for (; s0 + 8u <= nseq; s0 += 8u) lit_pass(s0, std::integral_constant<uint32_t, 8>{});
-#pragma unroll 1
-      for (; s0 < nseq; s0 += 2u) lit_pass(s0, std::integral_constant<uint32_t, 2>{});   // s0 + 1 <= 63
-      // literal runs longer than 64 bytes (rare): the rest, sequence by sequence
-      for (uint64_t lng = ballot(L > 64u); lng; lng &= lng - 1u) {
-        const uint32_t s = (uint32_t)__builtin_ctzll(lng);
-        const uint32_t Ls = readlane(L, s), pk = readlane(la, s);
-#pragma unroll 1
-        for (uint32_t j = 64u; j < Ls; j += 64u)
-          st8(src.u8((pk >> 16) + j + lane), j + lane < Ls, (pk & 0xffffu) + j + lane);
-      }
-      op += (int)(readlane(xi, 63) & 0xffffu);
+#if KDB_ABL_NO_EMIT   // (attribution build: the batch recorded but not encoded -- timing only, wrong output)
+      asm volatile("" ::"v"(rlm), "v"(roff));
+#else
+      op = (int)flush_seqs(src, out_rsrc, rlm, roff, nseq, banchor, (uint32_t)op);
+#endif
       banchor = anchor;
       nseq = 0;
     };
@@ -1152,11 +1355,21 @@ __device__ __forceinline__ int compress_block(Src& src, uint32_t S, const Tab& t
       }
     }
     if constexpr (kBatch) {
+#if !KDB_ABL_NO_EMIT
+      if constexpr (Hand::kOn) {
+        // nothing flushed yet, so the whole value is this one batch: a helper
+        // wave emits it, the last literals and the frame too
+        if (op == 0 && banchor == 0u && hand->push(rlm, roff, S, anchor, nseq)) return kUnsupported;
+      }
+#endif
       if (nseq) flush_batch();
     }
     if (kGuard && guard_fail) return 0;
   }
 
+#if KDB_ABL_NO_EMIT   // (attribution build: no last literals in the batched form -- timing only)
+  if constexpr (KDB_LZ4_BATCH_EMIT && kBatchE && Src::kUnclamped && !kGuard && !kWide) return unii((int)(S - anchor) + 1);
+#endif
   {  // the last literals (lz4.cc:625-637)
     const uint32_t run = S - anchor;
     if (kGuard && op + (int)run + 1 + (int)((run + 255u - kRunMask) / 255u) > cap) return 0;
@@ -1211,6 +1424,22 @@ __device__ __forceinline__ void stage_aligned(const uint8_t* g, uint32_t n, uint
 // goes), kEmitBatch (batched), or kEmitPerValue (two instances of the parse,
 // batched for values of kBatchMin bytes and more).
 constexpr uint32_t kEmitDirect = 0, kEmitBatch = 1, kEmitPerValue = 2;
+// Emission helper waves per workgroup of lz4_compress_kernel<F, kSmall, kEmit,
+// kWaves>: the batched multi-wave <= 4 KiB kernel has them (a constant of the
+// instantiation, not a template parameter of its own: the kernels keep the
+// names profiles and tests know them by).  Five, each serving two parse
+// waves: a helper emits a 4 KiB value's ~41 sequences from global memory in
+// several microseconds and a parse wave hands one off every ~19, so one helper
+// kept up with none of its ten waves' hand-offs (headline compress 8.01 ms
+// against the parent's 8.00), two with some (7.69), three 7.45, five
+// 7.31-7.35 ms (profiles/r07/r07_ab_helpers.txt).
+#ifndef KDB_LZ4_EMIT_NHELP
+#define KDB_LZ4_EMIT_NHELP 5
+#endif
+template <bool kSmall, uint32_t kEmit, uint32_t kWaves>
+constexpr uint32_t emit_helpers() {
+  return kSmall && kWaves > 1 && kEmit == kEmitBatch ? (uint32_t)KDB_LZ4_EMIT_NHELP : 0u;
+}
 // kWaves > 1 (kSmall only): `smem` is this wave's 16 KiB region of a workgroup
 // of kWaves independent waves (lz4_compress_kernel), so the workgroup's
 // barrier is no business of the value loop: LDS ordering within the wave is
@@ -1220,13 +1449,15 @@ __device__ __forceinline__ void value_sync() {
   if constexpr (kWaves == 1) __syncthreads();
   else __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
 }
-template <bool kFrame, bool kSmall, uint32_t kEmit, uint32_t kWaves = 1>
+template <bool kFrame, bool kSmall, uint32_t kEmit, uint32_t kWaves = 1, class Hand = NoHand>
 __device__ __forceinline__ void values_loop(
     uint8_t* const smem, const uint8_t* __restrict__ src, const uint64_t* __restrict__ src_off,
     const uint32_t* __restrict__ src_len, uint32_t n, uint32_t min_len, uint32_t in_cap,
     uint8_t* __restrict__ dst, const uint64_t* __restrict__ dst_off,
     const uint32_t* __restrict__ dst_cap, uint32_t* __restrict__ frame_len,
-    int32_t* __restrict__ ret, uint32_t* __restrict__ work, uint32_t batch, uint32_t nq, uint32_t guide) {
+    int32_t* __restrict__ ret, uint32_t* __restrict__ work, uint32_t batch, uint32_t nq, uint32_t guide,
+    Hand* hand = nullptr) {
+  static_assert(!Hand::kOn || (kSmall && kEmit == kEmitBatch), "emission helpers: the <= 4 KiB batched kernel");
   const uint32_t lane = lane_id();
   uint16_t* tab16 = reinterpret_cast<uint16_t*>(smem);
   constexpr uint32_t kTabBytes = kSmall ? kTable12Bytes : kTableBytes;
@@ -1316,19 +1547,32 @@ __device__ __forceinline__ void values_loop(
     value_sync<kWaves>();
 
     const uint32_t bound = compress_bound(S);
+    if constexpr (Hand::kOn) {
+      hand->v = v;
+      hand->peek();
+    }
     if (!kFrame) {
       const uint32_t cap = uni(dst_cap[v]);
       LdsSrc ls{s_in};
       const bool batch = kEmit == kEmitBatch || (kEmit == kEmitPerValue && S >= kBatchMin);
       const int r = cap < bound ? compress_block<false, true>(ls, S, tab, o, (int)cap, (int)cap)
-                    : batch     ? compress_block<false, false, kEmit != kEmitDirect>(ls, S, tab, o, (int)bound, (int)cap)
+                    : batch     ? compress_block<false, false, kEmit != kEmitDirect>(ls, S, tab, o, (int)bound, (int)cap, hand)
                                 : compress_block<false, false, kEmit == kEmitBatch>(ls, S, tab, o, (int)bound, (int)cap);
-      if (lane == 0) ret[v] = r;
+      // (kUnsupported: handed to a helper wave, whose status store follows the sentinel push() left)
+      if (lane == 0 && !(Hand::kOn && r == kUnsupported)) ret[v] = r;
     } else {
       LdsSrc ls{s_in};
       const bool batch = kEmit == kEmitBatch || (kEmit == kEmitPerValue && S >= kBatchMin);
-      const int r = batch ? compress_block<false, false, kEmit != kEmitDirect>(ls, S, tab, o + 8, (int)bound, (int)bound)
+      const int r = batch ? compress_block<false, false, kEmit != kEmitDirect>(ls, S, tab, o + 8, (int)bound, (int)bound, hand)
                           : compress_block<false, false, kEmit == kEmitBatch>(ls, S, tab, o + 8, (int)bound, (int)bound);
+      if (Hand::kOn && r == kUnsupported) {
+        // handed to a helper wave: it writes the block, the header, frame_len and the status
+      } else
+#if KDB_ABL_NO_EMIT   // (attribution build: the batched <= 4 KiB kernel writes no header and no status -- timing only)
+      if (kSmall && kEmit == kEmitBatch) {
+        asm volatile("" ::"s"(r));
+      } else
+#endif
       if (r <= 0) {                              // compressor.cc:31-34
         if (lane == 0) { ret[v] = -1; frame_len[v] = 0; }
       } else {
@@ -1353,6 +1597,7 @@ __device__ __forceinline__ void values_loop(
     value_sync<kWaves>();
     v = vn;
   }
+  if constexpr (Hand::kOn) hand->finish();
 }
 
 // kWaves (kSmall): waves per workgroup, each compressing its own values in its
@@ -1360,15 +1605,31 @@ __device__ __forceinline__ void values_loop(
 // (tools/probe/lds_occupancy, profiles/r05/r05_occ.txt): a one-wave workgroup
 // of 16 KiB takes 13 steps, so 9 fit a CU's 160 KiB; ten waves in one
 // workgroup of exactly 160 KiB hold 10 values per CU.
+//
+// kHelpers = emit_helpers<>() (the batched multi-wave kSmall kernel): emission
+// helper waves after the kWaves parse waves (see "emission helper waves" above).  They take no values from
+// the work queue and touch no LDS; the workgroup has no barrier, so a helper
+// that has nothing to do (eh.ring == nullptr: helpers off) simply leaves.
 template <bool kFrame, bool kSmall, uint32_t kEmit, uint32_t kWaves = 1>
-__global__ __launch_bounds__(64 * kWaves) void lz4_compress_kernel(
+__global__ __launch_bounds__(64 * (kWaves + emit_helpers<kSmall, kEmit, kWaves>())) void lz4_compress_kernel(
     const uint8_t* __restrict__ src, const uint64_t* __restrict__ src_off,
     const uint32_t* __restrict__ src_len, uint32_t n, uint32_t min_len, uint32_t in_cap,
     uint8_t* __restrict__ dst, const uint64_t* __restrict__ dst_off,
     const uint32_t* __restrict__ dst_cap, uint32_t* __restrict__ frame_len,
     int32_t* __restrict__ ret, uint32_t* __restrict__ work, uint32_t batch, const uint32_t* __restrict__ census,
-    uint32_t cls, uint32_t nq, uint32_t guide) {
+    uint32_t cls, uint32_t nq, uint32_t guide, EmitHelp eh) {
+  constexpr uint32_t kHelpers = emit_helpers<kSmall, kEmit, kWaves>();
+  static_assert(kWaves <= 64u && kWaves + kHelpers <= 16u, "a lane per parse wave; at most 1 024 threads");
   if (census && census[cls] == 0) return;      // no value of this size class in the batch
+  if constexpr (kHelpers != 0) {
+    const uint32_t wave = uni(threadIdx.x >> 6);
+    if (wave >= kWaves) {
+      if (eh.ring)
+        emit_helper_loop<kFrame, kWaves, kHelpers>(wave - kWaves, eh, src, src_off, n, in_cap, dst, dst_off, frame_len,
+                                                   ret);
+      return;
+    }
+  }
   // kSmall: a fixed LDS layout at LDS address 0 (the kernel's only LDS
   // array), so every LDS address is a constant offset (a dynamic
   // allocation's base costs a v_add per address); with several waves, wave w's
@@ -1379,8 +1640,16 @@ __global__ __launch_bounds__(64 * kWaves) void lz4_compress_kernel(
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_d[];
   uint8_t* smem = smem_d;
   if constexpr (kSmall) smem = kWaves > 1 ? smem_s + (kTable12Bytes + 4096u) * uni(threadIdx.x >> 6) : smem_s;
-  values_loop<kFrame, kSmall, kEmit, kWaves>(smem, src, src_off, src_len, n, min_len, in_cap, dst, dst_off,
-                                             dst_cap, frame_len, ret, work, batch, nq, guide);
+  if constexpr (kHelpers != 0) {
+    const uint32_t gw = blockIdx.x * kWaves + uni(threadIdx.x >> 6);
+    EmitHand hand{eh.ring ? eh.ring + (size_t)gw * kHandMaxRing * kHandSlotBytes : nullptr,
+                  eh.ctl + 2u * (size_t)gw, eh.depth, eh.gen, 0u, 0u, 0u, ret, 0ull};
+    values_loop<kFrame, kSmall, kEmit, kWaves>(smem, src, src_off, src_len, n, min_len, in_cap, dst, dst_off, dst_cap,
+                                               frame_len, ret, work, batch, nq, guide, &hand);
+  } else {
+    values_loop<kFrame, kSmall, kEmit, kWaves>(smem, src, src_off, src_len, n, min_len, in_cap, dst, dst_off,
+                                               dst_cap, frame_len, ret, work, batch, nq, guide);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1685,6 +1954,7 @@ static hipError_t launch_one(hipStream_t st, size_t lds, const uint8_t* src, con
                              uint32_t guide = 0) {
   static_assert(W == 1 || Sm, "multi-wave workgroups: the <= 4 KiB class");
   auto kern = lz4_compress_kernel<F, Sm, Em, W>;
+  constexpr uint32_t H = emit_helpers<Sm, Em, W>();   // helper waves per workgroup (the batched ten-wave kernel)
   // see kOffLaneLds: the off lanes' first address (Table12 at kT12Lo in the
   // static 16 KiB; Table16 at the dynamic allocation, after the 16 static
   // bytes) must lie past the whole allocation
@@ -1692,10 +1962,17 @@ static hipError_t launch_one(hipStream_t st, size_t lds, const uint8_t* src, con
   const size_t off_lane = Sm ? kOffLaneLds + kT12Lo : 16u + kOffLaneLds;
   if (W == 1 && alloc > off_lane) return hipErrorInvalidValue;
   if (W > 1 && lds != 0) return hipErrorInvalidValue;   // static LDS only (kOffLaneWG: nothing past 160 KiB)
-  const uint32_t grid = persistent_grid(reinterpret_cast<const void*>(kern), lds, n, W);
+  const uint32_t grid = persistent_grid(reinterpret_cast<const void*>(kern), lds, n, W, H);
   uint32_t* work = nullptr;
   hipError_t e = launch_counter(st, n, grid * W, &work);   // (waves >= values: wave b takes value b)
   if (e != hipSuccess) return e;
+  // the helpers' rings: a scratch set of this launch's own (ring == nullptr: helpers off)
+  EmitScratch es{};
+  if (H != 0 && (e = emit_scratch(st, grid * W, kHandMaxRing * kHandSlotBytes, &es)) != hipSuccess) {
+    (void)work_counter_release(st, work);
+    return e;
+  }
+  const EmitHelp eh{es.ring, es.ctl, es.depth, es.gen, es.cap_ticks};
   const uint32_t batch = claim_batch(n, grid * W);
   // the rocprof (demangled) name
   static const char* const names[2][2][3] = {
@@ -1710,11 +1987,12 @@ static hipError_t launch_one(hipStream_t st, size_t lds, const uint8_t* src, con
   static const std::string multi = std::string("lz4_compress_kernel<") + (F ? "true" : "false") + ", true, " +
                                    std::to_string(Em) + "u, " + std::to_string(W) + "u>";
   launch_note(W > 1 ? multi.c_str() : names[F][Sm][Em]);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * W), lds, st, src, src_off, src_len, n, min_len, in_cap, dst, dst_off,
-                     dst_cap, frame_len, ret, work, batch, census, cls, work_queues(in_cap), guide);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * (W + H)), lds, st, src, src_off, src_len, n, min_len, in_cap, dst,
+                     dst_off, dst_cap, frame_len, ret, work, batch, census, cls, work_queues(in_cap), guide, eh);
   e = hipGetLastError();
   const hipError_t r = work_counter_release(st, work);   // the slot is fenced even when the launch failed
-  return e != hipSuccess ? e : r;
+  const hipError_t r2 = emit_scratch_release(st, es);
+  return e != hipSuccess ? e : r != hipSuccess ? r : r2;
 }
 
 template <bool F, bool W>

@@ -227,7 +227,27 @@ hipError_t work_counter(hipStream_t st, uint32_t** ctr);
 // after the launches reading a counter slot are queued on st: fences the slot
 // against reuse (launch_util.hip)
 hipError_t work_counter_release(hipStream_t st, uint32_t* ctr);
-uint32_t persistent_grid(const void* kern, size_t lds, uint32_t n, uint32_t waves = 1);
+// helpers: waves per workgroup beside the `waves` that take values (they count
+// for the occupancy, not for the number of workgroups)
+uint32_t persistent_grid(const void* kern, size_t lds, uint32_t n, uint32_t waves = 1, uint32_t helpers = 0);
+// Global scratch of one launch of the batched <= 4 KiB compress kernel, through
+// which its parse waves hand emissions to the workgroup's helper waves
+// (lz4_compress.hip, "emission helper waves"): a ring of ring_bytes per parse
+// wave and two 64-bit words per parse wave, tagged with the launch's generation
+// so that nothing carries over from the set's last user.  Per device a few
+// sets, each fenced by an event like the counter slots.  ring == nullptr:
+// helpers off for this launch (KDB_LZ4_EMIT_HELPERS=0 in the environment, read
+// per launch, or more parse waves than a set holds).  KDB_LZ4_EMIT_RING=<1|2|4>
+// (read per launch too) sets the ring depth.
+struct EmitScratch {
+  uint8_t* ring = nullptr;
+  uint64_t* ctl = nullptr;
+  uint32_t depth = 0, gen = 0;
+  uint64_t cap_ticks = 0;   // the helpers' wall-clock cap (wall_clock64 ticks)
+  int set = -1;
+};
+hipError_t emit_scratch(hipStream_t st, uint32_t parse_waves, uint32_t ring_bytes, EmitScratch* es);
+hipError_t emit_scratch_release(hipStream_t st, const EmitScratch& es);
 // service waves (service.h) resident on `dev` right now (kdb_lz4_capi.hip)
 uint32_t services_resident(int dev);
 // The launch's work counter: a direct launch (n no larger than the resident

@@ -30,6 +30,9 @@ def main():
     ap.add_argument("--no-headline", action="store_true")
     ap.add_argument("--exact-max-in", action="store_true",
                     help="decompress told the batch's largest frame (not the slot bound)")
+    ap.add_argument("--compress-only", action="store_true",
+                    help="time the compress pass alone: no decompress, no digest, no round trip "
+                         "(attribution builds whose frames are wrong on purpose, e.g. -DKDB_ABL_NO_EMIT)")
     a = ap.parse_args()
     from kingdb_amd import _lib
     _lib.load(os.path.abspath(a.so))
@@ -49,6 +52,21 @@ def main():
         b = K.DeviceBatch.g1_long_sizes(sizes)
         st = K.Stream()
         b.exact_max_in = a.exact_max_in
+        if a.compress_only:
+            b.compress(st)
+            st.sync()
+            e = [K.Event() for _ in range(2)]
+            cs = []
+            for _ in range(a.reps):
+                e[0].record(st)
+                b.compress(st)
+                e[1].record(st)
+                cs.append(e[0].elapsed_ms(e[1]))
+            print(f"{os.path.basename(a.so):24s} {name:10s} compress min {min(cs):7.3f} med {np.median(cs):7.3f} "
+                  f"max {max(cs):7.3f} ms  reps {' '.join(f'{c:.3f}' for c in cs)}  (compress only, not checked)",
+                  flush=True)
+            b.free()
+            continue
         b.compress(st)
         b.decompress(st)
         st.sync()

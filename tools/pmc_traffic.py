@@ -78,14 +78,17 @@ def main():
         # classes (big / mixed kernels) also gather 4-byte candidate words and the
         # ring decoder refills with dword loads: for them the true read bytes lie
         # between the raw count and twice it, and both are reported.
-        narrow = any(t in nm for t in ("big_kernel", "big_compact_kernel", "mixed_kernel", "mixed24_kernel"))
+        # The batched ten-wave <= 4 KiB compressor (emission helper waves) reads each
+        # value a second time with byte loads (the literals), so it is a mix too.
+        narrow = any(t in nm for t in ("big_kernel", "big_compact_kernel", "mixed_kernel", "mixed24_kernel")) or \
+            ("lz4_compress_kernel<" in nm and ", 1u, 10u>" in nm)
         res["kernels"][k] = {
             "kernel": nm, "fetch_size_kib_raw": f, "write_size_kib_raw": w,
             "read_bytes_per_launch": rd, "write_bytes_per_launch": wr,
             "hbm_bytes_per_launch": None if rd is None or wr is None else rd + wr,
             "hbm_bytes_per_launch_undoubled": None if rd1 is None or wr is None else rd1 + wr,
             "correction": ("FETCH_SIZE x2 applies: every read is a 16 B-per-lane streaming load" if not narrow else
-                           "bounds: the launch mixes 16 B-per-lane streaming loads with 4-byte gathers, for "
+                           "bounds: the launch mixes 16 B-per-lane streaming loads with 4-byte gathers or byte loads, for "
                            "which the guide's x2 is uncalibrated; the true HBM bytes lie between "
                            "hbm_bytes_per_launch_undoubled and hbm_bytes_per_launch"),
         }
