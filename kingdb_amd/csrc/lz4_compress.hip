@@ -1429,8 +1429,9 @@ constexpr uint32_t kEmitDirect = 0, kEmitBatch = 1, kEmitPerValue = 2;
 // instantiation, not a template parameter of its own: the kernels keep the
 // names profiles and tests know them by).  Five, each serving two parse
 // waves: a helper emits a 4 KiB value's ~41 sequences from global memory in
-// several microseconds and a parse wave hands one off every ~19, so one helper
-// kept up with none of its ten waves' hand-offs (headline compress 8.01 ms
+// several microseconds and a parse wave hands one off every ~19 us -- a
+// workgroup's ten parse waves together one every ~2 us -- so one helper kept
+// up with none of its ten waves' hand-offs (headline compress 8.01 ms
 // against the parent's 8.00), two with some (7.69), three 7.45, five
 // 7.31-7.35 ms (profiles/r07/r07_ab_helpers.txt).
 #ifndef KDB_LZ4_EMIT_NHELP
@@ -1629,6 +1630,17 @@ __global__ __launch_bounds__(64 * (kWaves + emit_helpers<kSmall, kEmit, kWaves>(
                                                    ret);
       return;
     }
+    // The parse waves run above their workgroup's helper waves: the helpers
+    // share the parse waves' SIMDs (their vector work is +5 % of the kernel's),
+    // and a helper that loses an issue slot only finds its ring a little
+    // fuller, while a parse wave that loses one lengthens its chain.
+    // -DKDB_LZ4_PARSE_PRIO=0: off (A/B); DESIGN.md section 9 has the numbers.
+#ifndef KDB_LZ4_PARSE_PRIO
+#define KDB_LZ4_PARSE_PRIO 1
+#endif
+#if KDB_LZ4_PARSE_PRIO
+    __builtin_amdgcn_s_setprio(KDB_LZ4_PARSE_PRIO);
+#endif
   }
   // kSmall: a fixed LDS layout at LDS address 0 (the kernel's only LDS
   // array), so every LDS address is a constant offset (a dynamic
