@@ -27,10 +27,11 @@ from .lz4 import (  # noqa: F401
 )
 
 from .index import HSTableIndex  # noqa: F401,E402
+from .recover import recover_files  # noqa: F401,E402
 
 __all__ = [
     "HSTableIndex", "DeviceBatch", "DeviceBuffer", "Event", "Stream", "build_id", "compress_blocks", "compress_bound",
     "compress_frames", "compress_limited_output", "decompress_blocks", "decompress_frames",
     "decompress_safe_partial", "device_count", "frame_bound", "get_device", "last_kernels", "selftest",
-    "set_device",
+    "set_device", "recover_files",
 ]

@@ -113,6 +113,11 @@ SIGNATURES = {
     "kdb_hstable_dev_download": (_i, [_vp, _u32, _vp, _vp]),
     "kdb_hstable_dev_reset": (_i, [_vp]),
     "kdb_hstable_dev_feed": (_i, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+    # include/kdb_recover.h (files without a usable footer, recovered in device memory)
+    "kdb_hstable_recover_bound": (_u64, [_u64]),
+    "kdb_hstable_recover_scratch_bytes": (_u64, [_vp, _u32]),
+    "kdb_hstable_recover_files": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
+    "kdb_hstable_recover_files_timed": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp]),
     # link-time aliases of the reference's lz4.h names
     "LZ4_compressBound": (_i, [_i]),
     "LZ4_compress_limitedOutput": (_i, [_c.c_char_p, _vp, _i, _i]),

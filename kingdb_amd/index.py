@@ -2,7 +2,8 @@
 set of closed HSTable files and the batched lookup in front of the decoder.
 
   HSTableIndex(files)     uploads the files once and loads their offset arrays
-                          (HSTableManager::LoadDatabase / LoadFile)
+                          (HSTableManager::LoadDatabase / LoadFile); with
+                          recover=, files without a usable footer are recovered
   .get(keys, verify)      [(status, value bytes)]: StorageEngine::GetWithIndex /
                           GetEntry per key, then kdb_get_values_batch over the
                           resident files (Database::GetRaw)
@@ -18,8 +19,12 @@ set of closed HSTable files and the batched lookup in front of the decoder.
 
 status: 0 OK, NOTFOUND, DELETED (Database::Get reports NotFound), MULTIPART
 (MultipartRequired), or the decoder's -1 / -2 (see get.py).  Databases opened
-with compression enabled only; files without a usable footer are not
-recovered (`.file_status`).
+with compression enabled only.  A file without a usable footer (status -1 in
+`.file_status`: the newest file after a crash) is left out unless
+HSTableIndex(files, recover="reference" | "content") is asked to recover it on
+the device first (kingdb_amd/recover.py, HSTableManager::RecoverFile):
+`.recovered` maps its name to the report, its status becomes 0, and a file the
+reference would remove stays out with its status.
 """
 from __future__ import annotations
 
@@ -81,35 +86,79 @@ class _Borrowed:
 
 
 class HSTableIndex:
-    def __init__(self, files: dict[str, bytes], hash_type: int = 1, stream: Stream | None = None):
+    def __init__(self, files: dict[str, bytes], hash_type: int = 1, stream: Stream | None = None,
+                 recover: str | None = None):
+        from . import recover as rec
+        if recover is not None:
+            rec.scope_code(recover)
         self.names = sorted(files)
         self.hash_type = hash_type
+        self.recovered = {}              # name -> recover.Report of the files recovered at the load
         n = len(self.names)
         size = np.array([len(files[f]) for f in self.names], np.uint64)
-        off = np.zeros(n, np.uint64)
-        if n > 1:
-            off[1:] = np.cumsum((size[:-1] + 63) & ~np.uint64(63))
-        total = int(off[-1] + size[-1]) if n else 0
-        buf = np.zeros(total + 64, np.uint8)
-        for f, o in zip(self.names, off):
-            buf[int(o):int(o) + len(files[f])] = np.frombuffer(files[f], np.uint8)
-        self.file_off, self.file_size = off, size
+        # a slot holds the file; with `recover`, one whose last bytes hold no
+        # footer magic gets the room its recovery needs
+        cap = size.copy()
+        if recover is not None:
+            for i, f in enumerate(self.names):
+                b = files[f]
+                if len(b) > 8192 and (len(b) < 8192 + 36 or b[-12:-4] != b"WOEM\0\0\0\0"):
+                    cap[i] = rec.bound(len(b))
         self.fileid = np.array([int(f, 16) for f in self.names], np.uint32)
-        self.files = DeviceBuffer(total + 64)
+        self.files = None
         self.h = None
         self._scan = None                # (verify, live, key bytes, max key length) of the prepared scan
         st = stream.ptr if stream else None
-        self.files.upload(buf, stream=st)
+        self._upload(files, size, cap, st)
         h = ctypes.c_void_p()
         _lib.check(lib().kdb_index_create(hash_type, ctypes.byref(h)), "kdb_index_create")
         self.h = h.value
+        status = self._load(st)
+        torn = [i for i in range(n) if status[i] == -1]
+        if recover is not None and torn:
+            # HSTableManager::LoadDatabase: a file LoadFile refuses is recovered (RecoverFile), in its slot
+            relaid = any(cap[i] < rec.bound(int(size[i])) for i in torn)  # a footer with its magic and a bad CRC
+            if relaid:
+                for i in torn:
+                    cap[i] = rec.bound(int(size[i]))
+                self._upload(files, size, cap, st)
+            reports = rec.recover_resident(self.files.ptr, self.file_off[torn], size[torn], cap[torn], recover, stream)
+            for i, r in zip(torn, reports):
+                if r.status == 0:                                        # the others the reference removes
+                    self.file_size[i] = r.size
+                    self.recovered[self.names[i]] = r
+            # the handle holds the buffer and the offsets it was loaded over: after a new layout it is
+            # loaded again even where no file came back
+            if self.recovered or relaid:
+                self._load(st)
+
+    def _upload(self, files: dict[str, bytes], size: np.ndarray, cap: np.ndarray, st) -> None:
+        """The files into 64-byte-aligned slots of cap[i] bytes, in one buffer."""
+        n = len(self.names)
+        off = np.zeros(n, np.uint64)
+        if n > 1:
+            off[1:] = np.cumsum((cap[:-1] + np.uint64(63)) & ~np.uint64(63))
+        total = int(off[-1] + cap[-1]) if n else 0
+        buf = np.zeros(total + 64, np.uint8)
+        for f, o in zip(self.names, off):
+            buf[int(o):int(o) + len(files[f])] = np.frombuffer(files[f], np.uint8)
+        self.file_off, self.file_size = off, size.copy()
+        if self.files is not None:
+            self.files.free()
+        self.files = DeviceBuffer(total + 64)
+        self.files.upload(buf, stream=st)
+
+    def _load(self, st) -> np.ndarray:
+        n = len(self.names)
         status = np.zeros(max(n, 1), np.int32)
         entries = ctypes.c_uint64(0)
-        _lib.check(lib().kdb_index_load_files(self.h, st, self.files.ptr, off.ctypes.data, size.ctypes.data,
-                                              self.fileid.ctypes.data, n, status.ctypes.data, ctypes.byref(entries)),
-                   "kdb_index_load_files")
+        self._scan = None
+        _lib.check(lib().kdb_index_load_files(self.h, st, self.files.ptr, self.file_off.ctypes.data,
+                                              self.file_size.ctypes.data, self.fileid.ctypes.data, n,
+                                              status.ctypes.data, ctypes.byref(entries)), "kdb_index_load_files")
         self.file_status = {f: int(s) for f, s in zip(self.names, status[:n])}
         self.entries = entries.value
+        return status[:n]
 
     @classmethod
     def from_resident(cls, writer, stream: Stream | None = None) -> "HSTableIndex":
@@ -126,6 +175,7 @@ class HSTableIndex:
         self.file_off, self.file_size, self.fileid = off.copy(), size.copy(), fid.copy()
         self.files = _Borrowed(ptr, writer.arena)
         self._owner = writer
+        self.recovered = {}
         self.h = None
         self._scan = None
         n = len(fid)
