@@ -1,6 +1,7 @@
 // kingdb_amd/csrc/crc_device.h -- CRC32C on a wavefront (crc32c::Extend,
-// /root/reference/algorithm/crc32c.cc:296-340: reflected Castagnoli, register
-// pre/post-inverted), for the write path (put.hip) and the read path (get.hip).
+// algorithm/crc32c.cc:296-340: reflected Castagnoli, register pre/post-inverted),
+// for the write path (put.hip), the read path (get.hip) and the HSTable files
+// (index.hip, hstable_close.h, recover.hip).
 //
 // One message per wave: the message is seen as 64 equal lane chunks of 2^lg
 // bytes after zero padding at the FRONT (zero bytes leave a raw CRC register
@@ -82,6 +83,43 @@ __device__ uint32_t extend_wave(uint32_t init, uint64_t n, const Msg& msg, const
 
 __device__ __forceinline__ uint32_t step(uint32_t c, uint32_t byte, const uint32_t* s_t) {
   return s_t[(c ^ byte) & 0xffu] ^ (c >> 8);
+}
+
+// The plain message: bytes in memory.
+struct BytesMsg {
+  const uint8_t* p;
+  __device__ uint32_t feed(uint64_t a, uint64_t b, uint32_t c, const uint32_t* s_t) const {
+    for (uint64_t m = a; m < b; m++) c = crc::step(c, p[m], s_t);
+    return c;
+  }
+};
+
+// crc32c of bytes[0 .. n) by the kWaves waves of a workgroup, a contiguous part
+// each; the result on thread 0 (the others return 0).  s_crc: kWaves words,
+// free again on return.  Every thread of the workgroup calls it with the same
+// arguments: it contains __syncthreads(), so it has to be reached uniformly.
+template <uint32_t kWaves>
+__device__ __forceinline__ uint32_t extend_block(const uint8_t* bytes, uint64_t n, const uint32_t* s_t,
+                                                 uint32_t* s_crc) {
+  const uint64_t part = (n + kWaves - 1u) / kWaves;
+  const uint32_t w = threadIdx.x / 64u;
+  {
+    const uint64_t a = min((uint64_t)w * part, n), b = min(a + part, n);
+    const BytesMsg msg{bytes + a};
+    const uint32_t c = extend_wave(0u, b - a, msg, s_t);
+    if (lane_id() == 0) s_crc[w] = c;
+  }
+  __syncthreads();
+  uint32_t c = 0;
+  if (threadIdx.x == 0) {
+    c = s_crc[0];                             // crc(A || B) = crc(B) ^ shift(crc(A), |B|)
+    for (uint32_t k = 1; k < kWaves; k++) {
+      const uint64_t a = min((uint64_t)k * part, n), b = min(a + part, n);
+      c = s_crc[k] ^ crc::shift_n(c, b - a);
+    }
+  }
+  __syncthreads();                            // s_crc is free again
+  return c;
 }
 
 // Slice-by-4: t[k][i] is the register after byte i and k zero bytes, so four

@@ -39,7 +39,6 @@ hipError_t launch_compress(bool frame, hipStream_t st, const uint8_t* src, const
                            const uint32_t* src_len, uint32_t n, uint32_t min_len, uint32_t max_len, uint8_t* dst,
                            const uint64_t* dst_off, const uint32_t* dst_cap, uint32_t* frame_len,
                            int32_t* ret);
-hipError_t launch_exclusive_scan(hipStream_t st, const uint32_t* len, uint32_t n, uint64_t* off, uint64_t* total);
 
 namespace {
 
@@ -138,13 +137,6 @@ struct PartMsg {
     return c;
   }
 };
-struct KeyMsg {
-  const uint8_t* k;
-  __device__ uint32_t feed(uint64_t a, uint64_t b, uint32_t c, const uint32_t* s_t) const {
-    for (uint64_t m = a; m < b; m++) c = crc::step(c, k[m], s_t);
-    return c;
-  }
-};
 
 __device__ __forceinline__ PartMsg part_msg(const kdb_flush_part& P, const uint8_t* chunks, uint64_t chunk_off,
                                             const uint8_t* slots, uint64_t slot_off) {
@@ -201,7 +193,7 @@ __global__ __launch_bounds__(256) void flush_crc_kernel(
     const uint32_t p0 = uni(seg_first[s]), p1 = uni(seg_first[s + 1]);
     uint32_t c;
     if (offset_chunk[p0] == 0) {                   // :252-255
-      c = crc::extend_wave(0u, key_len[s], KeyMsg{keys + key_off[s]}, s_t);
+      c = crc::extend_wave(0u, key_len[s], crc::BytesMsg{keys + key_off[s]}, s_t);
     } else {                                       // continues the run's carried CRC
       uint32_t lo = 0, hi = nruns;                 // the run holding s: last r with run_first[r] <= s
       while (hi - lo > 1u) {

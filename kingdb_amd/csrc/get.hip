@@ -40,7 +40,6 @@ hipError_t launch_decompress(bool frame, hipStream_t st, const uint8_t* src, con
                              const uint32_t* in_len, uint32_t n, uint32_t max_in, uint32_t max_out,
                              uint8_t* dst, const uint64_t* dst_off, const uint32_t* out_cap,
                              const uint32_t* target, uint32_t* out_len, int32_t* ret);
-hipError_t launch_exclusive_scan(hipStream_t st, const uint32_t* len, uint32_t n, uint64_t* off, uint64_t* total);
 
 namespace {
 

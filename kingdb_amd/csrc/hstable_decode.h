@@ -34,6 +34,7 @@ constexpr uint32_t kTypeDelete = 0x1, kIsUncompacted = 0x2, kHasPadding = 0x4, k
 constexpr uint64_t kHeaderBlock = 8192;       // internal__hstable_header_size
 constexpr uint64_t kFooterSize = 36;          // HSTableFooter::GetFixedSize
 constexpr uint64_t kMagic = 0x4D454F57;       // HSTableManager::get_magic_number
+constexpr uint64_t kMaxFileSize = 0xFFFFFF00ull;   // entry offsets are 32-bit (OffsetArrayRow)
 constexpr uint32_t kMaxEntryHeader = 1 + 4 + 5 + 10 + 10 + 8 + 10 + 8;
 
 constexpr int kDecodeOk = 0, kDecodeError = -1, kDecodeChecksum = -2, kDecodeInvalid = -3;

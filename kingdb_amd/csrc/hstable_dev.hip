@@ -27,15 +27,18 @@
 //                        destination side (the alignbyte copy of pack.hip)
 //   hsd_header_kernel    workgroup per opened file: the header block
 //   hsd_crc_kernel       64 workgroups per closing file: CRC32C of a piece of
-//                        its rows (a part per wave, combined with the GF(2)
-//                        shift of crc_device.h)
-//   hsd_close_kernel     wave per closing file: the pieces' CRCs combined,
+//                        its rows (hstable_close.h, rows_piece_crc)
+//   hsd_close_kernel     wave per closing file: the pieces' CRCs joined,
 //                        extended over the footer's first 32 bytes, and the
-//                        footer
+//                        footer (hstable_close.h, close_file)
 // Every store into the arena is checked against the arena's size in the kernel
-// that makes it, whatever the plan or the caller's arrays say.
-// kdb_index_load_files shares nothing with this file but crc_device.h: it is
-// the independent check of what is written here.
+// that makes it, whatever the plan or the caller's arrays say.  The row
+// encoder and the closer are hstable_close.h's, shared with recover.hip; where
+// the rows lie and what the footer says is decided here.
+// kdb_index_load_files shares the CRC primitives (crc_device.h) and the format
+// constants (hstable_decode.h) with this file.  It still verifies every footer
+// CRC and parses every row with kernels and decode functions of its own:
+// decode_footer and encode_footer stay separate texts.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -46,22 +49,20 @@
 
 #include "../../include/kdb_put.h"
 #include "crc_device.h"
+#include "hip_host.h"
+#include "hstable_close.h"
 #include "hstable_cut.h"
 #include "lz4_device.h"
 
+namespace hs = kdb_hstable;
 namespace cut = kdb_hstable_cut;
+namespace hsc = kdb_hstable_close;
 
 namespace kdb_lz4 {
-
-hipError_t launch_exclusive_scan(hipStream_t st, const uint32_t* len, uint32_t n, uint64_t* off, uint64_t* total);
-
 namespace {
 
-constexpr uint64_t kFooter = 36;              // HSTableFooter::GetFixedSize
-constexpr uint64_t kMagic = 0x4D454F57;       // HSTableManager::get_magic_number
 constexpr uint32_t kHeadRecs = 64;            // records that come down with the head in one copy
 constexpr int kCloseBlock = 1024;             // hsd_crc_kernel: 16 waves share one piece's CRC
-constexpr uint32_t kCrcPieces = 64;           // workgroups per closing file's rows
 constexpr uint32_t kRefusedOffset = 1, kRefusedRecords = 2;
 
 struct PlanHead {
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(256) void hsd_rowlen_kernel(const PlanHead* __restr
       const cut::FileRec& f = recs[r];
       if (!(f.flags & cut::kIncomplete)) {
         const uint64_t off = f.fs + (P[i] - P[f.first]);
-        rl = cut::varint_len(hashed[i]) + cut::varint_len((uint32_t)off);
+        rl = hsc::row_len(hashed[i], (uint32_t)off);
       }
     }
     rowlen[i] = rl;
@@ -189,13 +190,9 @@ __global__ __launch_bounds__(256) void hsd_rows_kernel(uint8_t* __restrict__ are
     // forwards behind the entries, or backwards from the arena's end
     const bool staged = pl.rows_mode == kRowsStaged;
     const uint64_t off = f.fs + (P[i] - P[f.first]);
-    const uint32_t hl = cut::put_varint(hashed[i], [&](uint32_t k, uint8_t byte) {
+    hsc::put_row(hashed[i], (uint32_t)off, rl, [&](uint32_t k, uint8_t byte) {
       const uint64_t at = pos + k;
-      if (k < rl) arena[staged ? arena_bytes - 1u - at : at] = byte;
-    });
-    cut::put_varint((uint32_t)off, [&](uint32_t k, uint8_t byte) {
-      const uint64_t at = pos + hl + k;
-      if (hl + k < rl) arena[staged ? arena_bytes - 1u - at : at] = byte;
+      arena[staged ? arena_bytes - 1u - at : at] = byte;
     });
   }
 }
@@ -260,22 +257,7 @@ __global__ __launch_bounds__(256) void hsd_header_kernel(uint8_t* __restrict__ a
   }
 }
 
-struct BytesMsg {
-  const uint8_t* p;
-  __device__ uint32_t feed(uint64_t a, uint64_t b, uint32_t c, const uint32_t* s_t) const {
-    for (uint64_t m = a; m < b; m++) c = crc::step(c, p[m], s_t);
-    return c;
-  }
-};
-
-// A closing file's rows as kCrcPieces equal pieces, a workgroup each.
-__device__ __forceinline__ void crc_piece(uint64_t nbytes, uint32_t p, uint64_t* a, uint64_t* b) {
-  const uint64_t piece = (nbytes + kCrcPieces - 1u) / kCrcPieces;
-  *a = min((uint64_t)p * piece, nbytes);
-  *b = min(*a + piece, nbytes);
-}
-
-// crc32c of piece blockIdx.x % kCrcPieces of record blockIdx.x / kCrcPieces: a contiguous part per wave.
+// crc32c of piece blockIdx.x % kCrcPieces of the rows of record blockIdx.x / kCrcPieces.
 __global__ __launch_bounds__(kCloseBlock) void hsd_crc_kernel(const uint8_t* __restrict__ arena, uint64_t arena_bytes,
                                                               const cut::FileRec* __restrict__ recs,
                                                               const Place* __restrict__ places,
@@ -283,33 +265,16 @@ __global__ __launch_bounds__(kCloseBlock) void hsd_crc_kernel(const uint8_t* __r
   constexpr uint32_t kWaves = kCloseBlock / 64;
   __shared__ uint32_t s_t[256];
   __shared__ uint32_t s_crc[kWaves];
-  const uint32_t r = blockIdx.x / kCrcPieces, p = blockIdx.x % kCrcPieces;
+  const uint32_t r = blockIdx.x / hsc::kCrcPieces, p = blockIdx.x % hsc::kCrcPieces;
   const cut::FileRec f = recs[r];
   if ((f.flags & (cut::kCloses | cut::kIncomplete)) != cut::kCloses) return;
   const Place& pl = places[r];
   const uint64_t rows = pl.base + f.fs_end;
   if (!in_arena(rows, pl.rows_total, arena_bytes)) return;
-  uint64_t lo, hi;
-  crc_piece(pl.rows_total, p, &lo, &hi);
-  const uint64_t nbytes = hi - lo;
   crc::stage_table(s_t);
   __syncthreads();
-  const uint64_t part = (nbytes + kWaves - 1u) / kWaves;
-  const uint32_t w = threadIdx.x / 64u;
-  {
-    const uint64_t a = min((uint64_t)w * part, nbytes), b = min(a + part, nbytes);
-    const BytesMsg msg{arena + rows + lo + a};
-    const uint32_t c = crc::extend_wave(0u, b - a, msg, s_t);
-    if (lane_id() == 0) s_crc[w] = c;
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  uint32_t c = s_crc[0];                              // crc(A || B) = crc(B) ^ shift(crc(A), |B|)
-  for (uint32_t k = 1; k < kWaves; k++) {
-    const uint64_t a = min((uint64_t)k * part, nbytes), b = min(a + part, nbytes);
-    c = s_crc[k] ^ crc::shift_n(c, b - a);
-  }
-  piece_crc[(uint64_t)r * kCrcPieces + p] = c;
+  const uint32_t c = hsc::rows_piece_crc<kWaves>(arena + rows, pl.rows_total, p, s_t, s_crc);
+  if (threadIdx.x == 0) piece_crc[(uint64_t)r * hsc::kCrcPieces + p] = c;
 }
 
 // One wave per closing file: the pieces' CRCs joined, extended over the
@@ -324,29 +289,13 @@ __global__ __launch_bounds__(64) void hsd_close_kernel(uint8_t* __restrict__ are
   if ((f.flags & (cut::kCloses | cut::kIncomplete)) != cut::kCloses) return;
   const Place& pl = places[r];
   const uint64_t rows = pl.base + f.fs_end, nbytes = pl.rows_total;
-  if (!in_arena(rows, nbytes, arena_bytes) || !in_arena(rows + nbytes, kFooter, arena_bytes)) return;
+  if (!in_arena(rows, nbytes, arena_bytes) || !in_arena(rows + nbytes, hs::kFooterSize, arena_bytes)) return;
   crc::stage_table(s_t);
   __syncthreads();
   if (threadIdx.x != 0) return;
-  uint32_t c = piece_crc[(uint64_t)r * kCrcPieces];
-  for (uint32_t p = 1; p < kCrcPieces; p++) {
-    uint64_t lo, hi;
-    crc_piece(nbytes, p, &lo, &hi);
-    c = piece_crc[(uint64_t)r * kCrcPieces + p] ^ crc::shift_n(c, hi - lo);
-  }
-  // HSTableFooter (format.h:480-493): filetype, flags, offset of the rows, their number, magic; then
-  // crc32c::Extend over those 32 bytes
-  uint8_t ft[36];
-  const uint32_t w32[2] = {1u, (f.flags & cut::kPadding) ? 1u : 0u};
-  const uint64_t w64[3] = {f.fs_end, pl.nrows_total, kMagic};
-  for (uint32_t i = 0; i < 8u; i++) ft[i] = (uint8_t)(w32[i >> 2] >> (8u * (i & 3u)));
-  for (uint32_t i = 0; i < 24u; i++) ft[8u + i] = (uint8_t)(w64[i >> 3] >> (8u * (i & 7u)));
-  c ^= 0xFFFFFFFFu;
-  for (uint32_t i = 0; i < 32u; i++) c = crc::step(c, ft[i], s_t);
-  c ^= 0xFFFFFFFFu;
-  for (uint32_t i = 0; i < 4u; i++) ft[32u + i] = (uint8_t)(c >> (8u * i));
-  uint8_t* dst = arena + rows + nbytes;
-  for (uint32_t i = 0; i < 36u; i++) dst[i] = ft[i];
+  // filetype kUncompactedRegularType; the rows begin where the entries end
+  hsc::close_file(arena + rows, nbytes, piece_crc + (uint64_t)r * hsc::kCrcPieces, 1u,
+                  (f.flags & cut::kPadding) ? 1u : 0u, f.fs_end, pl.nrows_total, s_t);
 }
 
 // Compaction on the device (HSTableIndex.compacted_device): a scan window's
@@ -369,17 +318,6 @@ __global__ __launch_bounds__(256) void hsd_feed_kernel(const uint64_t* __restric
   if (ballot(bad) != 0 && lane_id() == 0) atomicOr(flag, 1u);
 }
 
-int hip_code(hipError_t e) {
-  if (e == hipSuccess) return KDB_PUT_OK;
-  return (e == hipErrorNoDevice || e == hipErrorInvalidDevice) ? KDB_PUT_ENODEV : KDB_PUT_EHIP;
-}
-
-#define KDB_TRY(expr)                     \
-  do {                                    \
-    const hipError_t e_ = (expr);         \
-    if (e_ != hipSuccess) return e_;      \
-  } while (0)
-
 uint32_t host_crc32c(const uint8_t* p, size_t n) {      // 20 bytes per file opened
   uint32_t c = 0xFFFFFFFFu;
   for (size_t i = 0; i < n; i++) {
@@ -390,9 +328,6 @@ uint32_t host_crc32c(const uint8_t* p, size_t n) {      // 20 bytes per file ope
 }
 void put32(uint8_t* p, uint32_t v) { for (int i = 0; i < 4; i++) p[i] = (uint8_t)(v >> (8 * i)); }
 void put64(uint8_t* p, uint64_t v) { for (int i = 0; i < 8; i++) p[i] = (uint8_t)(v >> (8 * i)); }
-
-uint64_t align64(uint64_t x) { return (x + 63u) & ~63ull; }
-uint64_t align256(uint64_t x) { return (x + 255u) & ~255ull; }
 
 }  // namespace
 }  // namespace kdb_lz4
@@ -457,7 +392,7 @@ Work carve(uint8_t* base, uint32_t n, uint32_t cap) {
   k.head = reinterpret_cast<PlanHead*>(take(sizeof(PlanHead) + (uint64_t)cap * sizeof(cut::FileRec)));
   k.recs = reinterpret_cast<cut::FileRec*>(base ? reinterpret_cast<uint8_t*>(k.head) + sizeof(PlanHead) : nullptr);
   k.places = reinterpret_cast<Place*>(take((uint64_t)cap * sizeof(Place)));
-  k.piece_crc = reinterpret_cast<uint32_t*>(take((uint64_t)cap * kCrcPieces * 4u));
+  k.piece_crc = reinterpret_cast<uint32_t*>(take((uint64_t)cap * hsc::kCrcPieces * 4u));
   k.bytes = at;
   return k;
 }
@@ -537,7 +472,7 @@ bool place_records(const kdb_hstable_dev* w, const cut::FileRec* recs, uint32_t 
         pl.rows_at = p.open_base + f.fs_end + p.staged;
         pl.rows_total = p.staged + rb;
         pl.nrows_total = p.open_rows + f.nvalid;
-        size += pl.rows_total + kFooter;
+        size += pl.rows_total + hs::kFooterSize;
         if (p.staged) {
           p.unstage_dst = p.open_base + f.fs_end;
           p.unstage_bytes = p.staged;
@@ -582,10 +517,6 @@ void commit(kdb_hstable_dev* w, const Placement& p) {
   w->file_id.insert(w->file_id.end(), p.file_id.begin(), p.file_id.end());
 }
 
-uint32_t grid_for(uint64_t n, uint32_t block, uint32_t most) {
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + block - 1u) / block, most));
-}
-
 // The kernels that write the arena, for records already placed (uploaded to k.recs / k.places).
 hipError_t write_files(kdb_hstable_dev* w, hipStream_t st, const Work& k, const Placement& p, uint32_t nrec,
                        const uint8_t* d_entries, const uint64_t* d_entry_off, const uint32_t* d_entry_len,
@@ -606,7 +537,7 @@ hipError_t write_files(kdb_hstable_dev* w, hipStream_t st, const Work& k, const 
   hipLaunchKernelGGL(hsd_header_kernel, dim3(nrec), dim3(256), 0, st, w->arena, w->arena_bytes, k.recs, k.places);
   KDB_TRY(hipGetLastError());
   if (!p.file_id.empty()) {                  // some file closes
-    hipLaunchKernelGGL(hsd_crc_kernel, dim3(kCrcPieces * nrec), dim3(kCloseBlock), 0, st, w->arena, w->arena_bytes,
+    hipLaunchKernelGGL(hsd_crc_kernel, dim3(hsc::kCrcPieces * nrec), dim3(kCloseBlock), 0, st, w->arena, w->arena_bytes,
                        k.recs, k.places, k.piece_crc);
     KDB_TRY(hipGetLastError());
     hipLaunchKernelGGL(hsd_close_kernel, dim3(nrec), dim3(64), 0, st, w->arena, w->arena_bytes, k.recs, k.places,
@@ -712,7 +643,7 @@ extern "C" uint64_t kdb_hstable_dev_arena_bytes(uint64_t hstable_size, uint64_t 
   if (n_entries > (1ull << 56) || entry_bytes > (1ull << 60)) return ~0ull;
   const uint64_t files = entry_bytes / (hstable_size - cut::kHeaderBlock) + 2u;
   if (files > (1ull << 48)) return ~0ull;
-  return align64(entry_bytes + 30u * n_entries + files * (cut::kHeaderBlock + kFooter + 64u));
+  return align64(entry_bytes + 30u * n_entries + files * (cut::kHeaderBlock + hs::kFooterSize + 64u));
 }
 
 extern "C" int kdb_hstable_dev_create(uint64_t hstable_size, uint32_t hash_type, uint64_t arena_bytes,

@@ -13,8 +13,8 @@
 //
 // Load (synchronous, like Database::Open):
 //   index_file_kernel    workgroup per file: HSTableHeader, footer, magic,
-//                        bounds, CRC32C of the offset array (wave CRC, the
-//                        waves' parts combined with the GF(2) shift)
+//                        bounds, CRC32C of the offset array and the footer's
+//                        first 32 bytes (crc::extend_block, crc_device.h)
 //   host                 files ordered by (timestamp, fileid); the exclusive
 //                        sum of num_entries numbers every row (its insertion
 //                        order into the reference's multimap)
@@ -57,15 +57,13 @@
 #include "../../include/kdb_put.h"
 #include "crc_device.h"
 #include "hash_device.h"
+#include "hip_host.h"
 #include "hstable_decode.h"
 #include "lz4_device.h"
 
 namespace hs = kdb_hstable;
 
 namespace kdb_lz4 {
-
-hipError_t launch_exclusive_scan(hipStream_t st, const uint32_t* len, uint32_t n, uint64_t* off, uint64_t* total);
-
 namespace {
 
 constexpr int kFileBlock = 1024;           // index_file_kernel: 16 waves share one file's CRC
@@ -74,7 +72,6 @@ constexpr int kGetBlock = 256;
 constexpr uint32_t kKeyStage = 256;        // query keys up to this many bytes are hashed from LDS
 constexpr uint32_t kHeaderStage = 64;      // >= hs::kMaxEntryHeader, one byte per lane
 static_assert(kHeaderStage >= hs::kMaxEntryHeader && kHeaderStage <= 64, "one load per lane covers a header");
-constexpr uint64_t kMaxFileSize = 0xFFFFFF00ull;   // entry offsets are 32-bit (OffsetArrayRow)
 constexpr uint64_t kMaxRows = 1ull << 30;
 
 struct FileRec {
@@ -99,14 +96,6 @@ struct Slot {
   uint32_t offset;       // entry offset in the file
   uint32_t seq;          // insertion order into the reference's multimap
   uint32_t pad;
-};
-
-struct BytesMsg {
-  const uint8_t* p;
-  __device__ uint32_t feed(uint64_t a, uint64_t b, uint32_t c, const uint32_t* s_t) const {
-    for (uint64_t m = a; m < b; m++) c = crc::step(c, p[m], s_t);
-    return c;
-  }
 };
 
 __global__ __launch_bounds__(kFileBlock) void index_file_kernel(const uint8_t* __restrict__ files,
@@ -153,24 +142,10 @@ __global__ __launch_bounds__(kFileBlock) void index_file_kernel(const uint8_t* _
     if (threadIdx.x == 0) rec[f] = s_rec;
     return;
   }
-  // CRC32C over [offset_indexes, size - 4) (LoadFile:1068): a contiguous part per wave
+  // CRC32C over [offset_indexes, size - 4) (LoadFile:1068); s_rec.status is the same for every thread
   const uint64_t oi = s_rec.offset_indexes;
-  const uint64_t n = size - 4u - oi;                 // oi <= size - 36
-  const uint64_t part = (n + kWaves - 1u) / kWaves;
-  const uint32_t w = threadIdx.x / 64u;
-  {
-    const uint64_t a = min((uint64_t)w * part, n), b = min(a + part, n);
-    const BytesMsg msg{p + oi + a};
-    const uint32_t c = crc::extend_wave(0u, b - a, msg, s_t);
-    if (lane_id() == 0) s_crc[w] = c;
-  }
-  __syncthreads();
+  const uint32_t c = crc::extend_block<kWaves>(p + oi, size - 4u - oi, s_t, s_crc);   // oi <= size - 36
   if (threadIdx.x == 0) {
-    uint32_t c = s_crc[0];                           // crc(A || B) = crc(B) ^ shift(crc(A), |B|)
-    for (uint32_t k = 1; k < kWaves; k++) {
-      const uint64_t a = min((uint64_t)k * part, n), b = min(a + part, n);
-      c = s_crc[k] ^ crc::shift_n(c, b - a);
-    }
     FileRec r = s_rec;
     const uint64_t rows_bytes = size - hs::kFooterSize - oi;
     if (c != s_want) r.status = -1;
@@ -397,7 +372,7 @@ __global__ __launch_bounds__(kGetBlock) void index_get_kernel(
           o_svc = hd.size_value_compressed;
           o_size = hd.size_value;
           o_ck = hd.checksum_content;
-          const BytesMsg msg{key};                               // == the stored key
+          const crc::BytesMsg msg{key};                               // == the stored key
           o_ci = crc::extend_wave(0u, klen, msg, s_t);          // storage_engine.h:497-500
         }
         break;
@@ -667,7 +642,7 @@ __global__ __launch_bounds__(kGetBlock) void index_scan_emit_kernel(
         o_svc = hd.size_value_compressed;
         o_size = hd.size_value;
         o_ck = hd.checksum_content;
-        const BytesMsg msg{key};
+        const crc::BytesMsg msg{key};
         o_ci = crc::extend_wave(0u, klen, msg, s_t);          // storage_engine.h:497-500
       }
     }
@@ -754,11 +729,6 @@ void index_release(kdb_index* ix) {
   ix->fileid.clear();
 }
 
-int hip_code(hipError_t e) {
-  if (e == hipSuccess) return KDB_PUT_OK;
-  return (e == hipErrorNoDevice || e == hipErrorInvalidDevice) ? KDB_PUT_ENODEV : KDB_PUT_EHIP;
-}
-
 // Temporaries of one load, freed on every way out.
 struct LoadTemps {
   FileRec* d_rec = nullptr;
@@ -778,12 +748,6 @@ struct LoadTemps {
     dfree(d_count);
   }
 };
-
-#define KDB_TRY(expr)                     \
-  do {                                    \
-    const hipError_t e_ = (expr);         \
-    if (e_ != hipSuccess) return e_;      \
-  } while (0)
 
 template <class T>
 hipError_t upload(hipStream_t st, T** d, const T* h, size_t n) {
@@ -942,7 +906,7 @@ extern "C" int kdb_index_load_files(kdb_index* ix, void* stream, const uint8_t* 
   if (!ix || (nfiles && (!d_files || !file_off || !file_size || !fileid || !file_status_out)))
     return KDB_PUT_EINVAL;
   for (uint32_t f = 0; f < nfiles; f++)
-    if (file_size[f] > kMaxFileSize) return KDB_PUT_EINVAL;
+    if (file_size[f] > hs::kMaxFileSize) return KDB_PUT_EINVAL;
   index_release(ix);
   bool too_many = false;
   const hipError_t e = index_load(ix, (hipStream_t)stream, d_files, file_off, file_size, fileid, nfiles,

@@ -227,6 +227,9 @@ hipError_t work_counter(hipStream_t st, uint32_t** ctr);
 // after the launches reading a counter slot are queued on st: fences the slot
 // against reuse (launch_util.hip)
 hipError_t work_counter_release(hipStream_t st, uint32_t* ctr);
+// off[i] = len[0] + .. + len[i - 1] for i < n, *total = the sum of all n;
+// total may be off + n (pack.hip)
+hipError_t launch_exclusive_scan(hipStream_t st, const uint32_t* len, uint32_t n, uint64_t* off, uint64_t* total);
 // helpers: waves per workgroup beside the `waves` that take values (they count
 // for the occupancy, not for the number of workgroups)
 uint32_t persistent_grid(const void* kern, size_t lds, uint32_t n, uint32_t waves = 1, uint32_t helpers = 0);

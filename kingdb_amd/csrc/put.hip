@@ -51,7 +51,6 @@ hipError_t launch_compress(bool frame, hipStream_t st, const uint8_t* src, const
                            const uint32_t* src_len, uint32_t n, uint32_t min_len, uint32_t max_len, uint8_t* dst,
                            const uint64_t* dst_off, const uint32_t* dst_cap, uint32_t* frame_len,
                            int32_t* ret);
-hipError_t launch_exclusive_scan(hipStream_t st, const uint32_t* len, uint32_t n, uint64_t* off, uint64_t* total);
 
 namespace {
 

@@ -34,8 +34,8 @@
 //                         hash, flags, CRC range, checksum_content)
 //   recover_crc_kernel    wave per entry with kIsUncompacted: CRC32C of its
 //                         range against checksum_content; ranges above 32 KiB
-//                         go to recover_crc_big_kernel, a workgroup whose 16
-//                         waves take a contiguous part each (crc::shift_n)
+//                         go to recover_crc_big_kernel, a workgroup of 16
+//                         waves (crc::extend_block, crc_device.h)
 //   recover_rowlen_kernel thread per entry: the length of its row if kept
 //   scan x 2              where each row starts; how many are kept
 //   recover_rows_kernel   thread per kept entry: varint64(hash) varint32(offset)
@@ -43,6 +43,9 @@
 //   recover_rowcrc_kernel 64 workgroups per file: CRC32C of a piece of its rows
 //   recover_close_kernel  wave per file: the pieces' CRCs joined and extended
 //                         over the footer's first 32 bytes, the footer, the report
+// The row encoder and the closer (the last two kernels' work) are
+// hstable_close.h's, shared with the device writer; which rows a file keeps,
+// where they lie in its slot (rows_of) and the footer's fields are decided here.
 // Every store into a slot is checked against the slot's capacity in the
 // kernel that makes it.  All temporaries live in the caller's scratch.
 #include <hip/hip_runtime.h>
@@ -55,17 +58,15 @@
 #include "../../include/kdb_put.h"
 #include "../../include/kdb_recover.h"
 #include "crc_device.h"
-#include "hstable_cut.h"
+#include "hip_host.h"
+#include "hstable_close.h"
 #include "hstable_recover.h"
 #include "lz4_device.h"
 
 namespace hs = kdb_hstable;
-namespace cut = kdb_hstable_cut;
+namespace hsc = kdb_hstable_close;
 
 namespace kdb_lz4 {
-
-hipError_t launch_exclusive_scan(hipStream_t st, const uint32_t* len, uint32_t n, uint64_t* off, uint64_t* total);
-
 namespace {
 
 constexpr uint32_t kTile = 4096;             // file positions per workgroup
@@ -76,8 +77,6 @@ constexpr uint32_t kGroup = 32;              // tiles per hop of the sequential 
 constexpr uint32_t kMaxSteps = kTile / (uint32_t)hs::kMinEntry + 2u;   // entries of one chain inside a tile
 constexpr int kBigBlock = 1024;              // recover_crc_big_kernel / recover_rowcrc_kernel: 16 waves
 constexpr uint64_t kBigCrc = 32768;          // CRC ranges above this take a workgroup
-constexpr uint32_t kCrcPieces = 64;          // workgroups per file's rows (recover_rowcrc_kernel)
-constexpr uint64_t kMaxFileSize = 0xFFFFFF00ull;   // entry offsets are 32-bit (OffsetArrayRow)
 constexpr uint32_t kEntCheck = 1, kEntPadding = 2;
 constexpr uint32_t kHdrLarge = 1, kHdrBad = 2;  // large type (RecoverFile gives up); no usable header (LoadDatabase skips)
 
@@ -342,14 +341,6 @@ __global__ __launch_bounds__(64) void recover_list_kernel(const uint8_t* __restr
   if (!kWrite) tile_count[t] = count;
 }
 
-struct BytesMsg {
-  const uint8_t* p;
-  __device__ uint32_t feed(uint64_t a, uint64_t b, uint32_t c, const uint32_t* s_t) const {
-    for (uint64_t m = a; m < b; m++) c = crc::step(c, p[m], s_t);
-    return c;
-  }
-};
-
 __global__ __launch_bounds__(256) void recover_crc_kernel(const uint8_t* __restrict__ d_files,
                                                           const FileIn* __restrict__ files, Entries E, uint32_t n) {
   __shared__ uint32_t s_t[256];
@@ -363,35 +354,10 @@ __global__ __launch_bounds__(256) void recover_crc_kernel(const uint8_t* __restr
     const FileIn& F = files[E.file[e]];
     const uint64_t begin = E.begin[e];
     if (begin > F.size || len > F.size - begin) continue;
-    const BytesMsg msg{d_files + F.off + begin};
+    const crc::BytesMsg msg{d_files + F.off + begin};
     const uint32_t c = crc::extend_wave(0u, len, msg, s_t);
     if (lane_id() == 0) E.keep[e] = c == E.want[e] ? 1u : 0u;
   }
-}
-
-// crc32c of bytes[0 .. n) by the 16 waves of a workgroup, a contiguous part
-// each; the result on thread 0 (the others return 0).  s_crc: 16 words.
-__device__ __forceinline__ uint32_t crc_block(const uint8_t* bytes, uint64_t n, const uint32_t* s_t, uint32_t* s_crc) {
-  constexpr uint32_t kWaves = kBigBlock / 64;
-  const uint64_t part = (n + kWaves - 1u) / kWaves;
-  const uint32_t w = threadIdx.x / 64u;
-  {
-    const uint64_t a = min((uint64_t)w * part, n), b = min(a + part, n);
-    const BytesMsg msg{bytes + a};
-    const uint32_t c = crc::extend_wave(0u, b - a, msg, s_t);
-    if (lane_id() == 0) s_crc[w] = c;
-  }
-  __syncthreads();
-  uint32_t c = 0;
-  if (threadIdx.x == 0) {
-    c = s_crc[0];                             // crc(A || B) = crc(B) ^ shift(crc(A), |B|)
-    for (uint32_t k = 1; k < kWaves; k++) {
-      const uint64_t a = min((uint64_t)k * part, n), b = min(a + part, n);
-      c = s_crc[k] ^ crc::shift_n(c, b - a);
-    }
-  }
-  __syncthreads();                            // s_crc is free again
-  return c;
 }
 
 __global__ __launch_bounds__(kBigBlock) void recover_crc_big_kernel(const uint8_t* __restrict__ d_files,
@@ -408,14 +374,14 @@ __global__ __launch_bounds__(kBigBlock) void recover_crc_big_kernel(const uint8_
     const FileIn& F = files[E.file[e]];
     const uint64_t begin = E.begin[e];
     if (begin > F.size || len > F.size - begin) continue;
-    const uint32_t c = crc_block(d_files + F.off + begin, len, s_t, s_crc);
+    const uint32_t c = crc::extend_block<kBigBlock / 64>(d_files + F.off + begin, len, s_t, s_crc);
     if (threadIdx.x == 0) E.keep[e] = c == E.want[e] ? 1u : 0u;
   }
 }
 
 __global__ __launch_bounds__(256) void recover_rowlen_kernel(Entries E, uint32_t n, FileState* __restrict__ state) {
   for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) {
-    E.rowlen[e] = E.keep[e] ? cut::varint_len(E.hash[e]) + cut::varint_len(E.off[e]) : 0u;
+    E.rowlen[e] = E.keep[e] ? hsc::row_len(E.hash[e], E.off[e]) : 0u;
     if (E.flags[e] & kEntPadding) atomicOr(&state[E.file[e]].footer_flags, hs::kFooterHasPadding);
   }
 }
@@ -434,20 +400,8 @@ __global__ __launch_bounds__(256) void recover_rows_kernel(uint8_t* __restrict__
     const uint64_t pos = (uint64_t)state[f].trunc + (R[e] - R[first]);
     if (pos > F.cap || rl > F.cap - pos) continue;
     uint8_t* dst = d_files + F.off + pos;
-    const uint32_t hl = cut::put_varint(E.hash[e], [&](uint32_t k, uint8_t byte) {
-      if (k < rl) dst[k] = byte;
-    });
-    cut::put_varint(E.off[e], [&](uint32_t k, uint8_t byte) {
-      if (hl + k < rl) dst[hl + k] = byte;
-    });
+    hsc::put_row(E.hash[e], E.off[e], rl, [&](uint32_t k, uint8_t byte) { dst[k] = byte; });
   }
-}
-
-// A file's rows as kCrcPieces equal pieces, a workgroup each.
-__device__ __forceinline__ void crc_piece(uint64_t nbytes, uint32_t p, uint64_t* a, uint64_t* b) {
-  const uint64_t piece = (nbytes + kCrcPieces - 1u) / kCrcPieces;
-  *a = min((uint64_t)p * piece, nbytes);
-  *b = min(*a + piece, nbytes);
 }
 
 // Where a recovered file's rows lie and how many they are; false for a file
@@ -475,16 +429,14 @@ __global__ __launch_bounds__(kBigBlock) void recover_rowcrc_kernel(const uint8_t
                                                                    uint32_t* __restrict__ piece_crc) {
   __shared__ uint32_t s_t[256];
   __shared__ uint32_t s_crc[kBigBlock / 64];
-  const uint32_t f = blockIdx.x / kCrcPieces, p = blockIdx.x % kCrcPieces;
+  const uint32_t f = blockIdx.x / hsc::kCrcPieces, p = blockIdx.x % hsc::kCrcPieces;
   const FileIn F = files[f];
   Rows rows;
   if (!rows_of(F, state[f], tile_prefix, R, K, &rows)) return;
-  uint64_t lo, hi;
-  crc_piece(rows.nbytes, p, &lo, &hi);
   crc::stage_table(s_t);
   __syncthreads();
-  const uint32_t c = crc_block(d_files + F.off + rows.at + lo, hi - lo, s_t, s_crc);
-  if (threadIdx.x == 0) piece_crc[(uint64_t)f * kCrcPieces + p] = c;
+  const uint32_t c = hsc::rows_piece_crc<kBigBlock / 64>(d_files + F.off + rows.at, rows.nbytes, p, s_t, s_crc);
+  if (threadIdx.x == 0) piece_crc[(uint64_t)f * hsc::kCrcPieces + p] = c;
 }
 
 // Wave per file: the pieces' CRCs joined, extended over the footer's first 32
@@ -514,25 +466,9 @@ __global__ __launch_bounds__(64) void recover_close_kernel(uint8_t* __restrict__
   crc::stage_table(s_t);
   __syncthreads();
   if (threadIdx.x != 0) return;
-  uint32_t c = piece_crc[(uint64_t)f * kCrcPieces];                        // crc(A || B) = crc(B) ^ shift(crc(A), |B|)
-  for (uint32_t p = 1; p < kCrcPieces; p++) {
-    uint64_t lo, hi;
-    crc_piece(rows.nbytes, p, &lo, &hi);
-    c = piece_crc[(uint64_t)f * kCrcPieces + p] ^ crc::shift_n(c, hi - lo);
-  }
-  // HSTableFooter (format.h:480-493), then crc32c::Extend over its first 32 bytes
   const uint32_t flags = (S.footer_flags & hs::kFooterHasPadding) | (rows.kept < rows.walked ? hs::kFooterHasInvalid : 0u);
-  uint8_t ft[36];
-  const uint32_t w32[2] = {S.filetype, flags};
-  const uint64_t w64[3] = {rows.at, rows.kept, hs::kMagic};
-  for (uint32_t i = 0; i < 8u; i++) ft[i] = (uint8_t)(w32[i >> 2] >> (8u * (i & 3u)));
-  for (uint32_t i = 0; i < 24u; i++) ft[8u + i] = (uint8_t)(w64[i >> 3] >> (8u * (i & 7u)));
-  c ^= 0xFFFFFFFFu;
-  for (uint32_t i = 0; i < 32u; i++) c = crc::step(c, ft[i], s_t);
-  c ^= 0xFFFFFFFFu;
-  for (uint32_t i = 0; i < 4u; i++) ft[32u + i] = (uint8_t)(c >> (8u * i));
-  uint8_t* dst = d_files + F.off + rows.at + rows.nbytes;
-  for (uint32_t i = 0; i < 36u; i++) dst[i] = ft[i];
+  hsc::close_file(d_files + F.off + rows.at, rows.nbytes, piece_crc + (uint64_t)f * hsc::kCrcPieces, S.filetype, flags,
+                  rows.at, rows.kept, s_t);
   FileState O = S;
   O.status = 0;
   O.new_size = rows.at + rows.nbytes + hs::kFooterSize;
@@ -541,19 +477,6 @@ __global__ __launch_bounds__(64) void recover_close_kernel(uint8_t* __restrict__
   O.footer_flags = flags;
   state[f] = O;
 }
-
-int hip_code(hipError_t e) {
-  if (e == hipSuccess) return KDB_PUT_OK;
-  return (e == hipErrorNoDevice || e == hipErrorInvalidDevice) ? KDB_PUT_ENODEV : KDB_PUT_EHIP;
-}
-
-#define KDB_TRY(expr)                     \
-  do {                                    \
-    const hipError_t e_ = (expr);         \
-    if (e_ != hipSuccess) return e_;      \
-  } while (0)
-
-uint64_t align256(uint64_t x) { return (x + 255u) & ~255ull; }
 
 // The scratch's arrays for files of these sizes.
 struct Scratch {
@@ -570,7 +493,7 @@ bool carve(uint8_t* base, const uint64_t* file_size, uint32_t nfiles, Scratch* o
   Scratch k{};
   if (nfiles > (1u << 20)) return false;     // kCrcPieces workgroups per file in one grid
   for (uint32_t f = 0; f < nfiles; f++) {
-    if (file_size[f] >= kMaxFileSize) return false;
+    if (file_size[f] >= hs::kMaxFileSize) return false;
     if (file_size[f] <= hs::kHeaderBlock) continue;
     const uint64_t body = file_size[f] - hs::kHeaderBlock;
     k.positions += body;
@@ -593,7 +516,7 @@ bool carve(uint8_t* base, const uint64_t* file_size, uint32_t nfiles, Scratch* o
   k.tile_entry = reinterpret_cast<uint32_t*>(take(k.ntiles * 4u));
   k.tile_count = reinterpret_cast<uint32_t*>(take(k.ntiles * 4u));
   k.tile_prefix = reinterpret_cast<uint64_t*>(take((k.ntiles + 1u) * 8u));
-  k.piece_crc = reinterpret_cast<uint32_t*>(take((uint64_t)nfiles * kCrcPieces * 4u));
+  k.piece_crc = reinterpret_cast<uint32_t*>(take((uint64_t)nfiles * hsc::kCrcPieces * 4u));
   uint32_t** u32s[] = {&k.E.off, &k.E.file, &k.E.flags, &k.E.begin, &k.E.len, &k.E.want, &k.E.keep, &k.E.rowlen};
   for (uint32_t** p : u32s) *p = reinterpret_cast<uint32_t*>(take(k.cap * 4u));
   k.E.hash = reinterpret_cast<uint64_t*>(take(k.cap * 8u));
@@ -602,10 +525,6 @@ bool carve(uint8_t* base, const uint64_t* file_size, uint32_t nfiles, Scratch* o
   k.bytes = at;
   *out = k;
   return true;
-}
-
-uint32_t grid_for(uint64_t n, uint32_t per_block, uint32_t most) {
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + per_block - 1u) / per_block, most));
 }
 
 // The timing events of a call that asks for its parts' times (ms != nullptr).
@@ -698,7 +617,7 @@ hipError_t recover(hipStream_t st, uint8_t* d_files, const uint64_t* file_off, c
     KDB_TRY(hipGetLastError());
   }
   if (n) {
-    hipLaunchKernelGGL(recover_rowcrc_kernel, dim3(nfiles * kCrcPieces), dim3(kBigBlock), 0, st, d_files, k.files,
+    hipLaunchKernelGGL(recover_rowcrc_kernel, dim3(nfiles * hsc::kCrcPieces), dim3(kBigBlock), 0, st, d_files, k.files,
                        k.state, k.tile_prefix, k.R, k.K, k.piece_crc);
     KDB_TRY(hipGetLastError());
   }
@@ -742,7 +661,7 @@ extern "C" int kdb_hstable_recover_files_timed(void* stream, uint8_t* d_files, c
       (reinterpret_cast<uintptr_t>(d_scratch) & 255u))
     return KDB_PUT_EINVAL;
   for (uint32_t f = 0; f < nfiles; f++)
-    if (file_size[f] >= kMaxFileSize || (file_off[f] & 3u) || file_cap[f] < hs::recover_bound(file_size[f]))
+    if (file_size[f] >= hs::kMaxFileSize || (file_off[f] & 3u) || file_cap[f] < hs::recover_bound(file_size[f]))
       return KDB_PUT_EINVAL;
   Scratch k;
   if (!carve(static_cast<uint8_t*>(d_scratch), file_size, nfiles, &k) || scratch_bytes < k.bytes) return KDB_PUT_EINVAL;

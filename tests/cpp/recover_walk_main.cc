@@ -1,6 +1,7 @@
 // tests/cpp/recover_walk_main.cc -- csrc/hstable_recover.h on the host, as a
 // stand-alone program: the sequential recovery walk, entry after entry, and
-// the file it leaves (truncated, fresh offset array, footer).  Built under
+// the file it leaves (truncated, fresh offset array, footer: the encoders of
+// csrc/hstable_close.h that the kernels use, on the host).  Built under
 // AddressSanitizer / UBSan by tests/test_recover_model.py, and -O2 without
 // them as the one-thread baseline of tools/bench_recover.py.  Every file sits
 // in a heap block of exactly its size, so a read outside it is a sanitizer
@@ -20,9 +21,11 @@
 #include <cstring>
 #include <vector>
 
+#include "../../kingdb_amd/csrc/hstable_close.h"
 #include "../../kingdb_amd/csrc/hstable_recover.h"
 
 namespace hs = kdb_hstable;
+namespace hsc = kdb_hstable_close;
 
 static uint32_t g_table[8][256];
 
@@ -53,17 +56,6 @@ static uint32_t crc32c(uint32_t init, const uint8_t* p, uint64_t n) {
   return c ^ 0xFFFFFFFFu;
 }
 
-static void put_varint(std::vector<uint8_t>& out, uint64_t v) {
-  while (v >= 128u) {
-    out.push_back((uint8_t)(v | 128u));
-    v >>= 7;
-  }
-  out.push_back((uint8_t)v);
-}
-static void put_fixed(std::vector<uint8_t>& out, uint64_t v, int n) {
-  for (int i = 0; i < n; i++) out.push_back((uint8_t)(v >> (8 * i)));
-}
-
 struct Result {
   int status = 0;
   uint64_t walked = 0, kept = 0, offset = 0;
@@ -90,8 +82,10 @@ static Result recover(const uint8_t* p, uint64_t n, uint32_t scope) {
         if (h.flags & hs::kHasPadding) padding = true;
         if (!kept) return;
         r.kept++;
-        put_varint(r.tail, h.hash);
-        put_varint(r.tail, (uint32_t)offset);
+        const size_t at = r.tail.size();
+        const uint32_t rl = hsc::row_len(h.hash, (uint32_t)offset);
+        r.tail.resize(at + rl);
+        hsc::put_row(h.hash, (uint32_t)offset, rl, [&](uint32_t k, uint8_t byte) { r.tail[at + k] = byte; });
       });
   r.flags = (padding ? hs::kFooterHasPadding : 0u) | (r.kept < r.walked ? hs::kFooterHasInvalid : 0u);
   if (r.offset <= hs::kHeaderBlock) {
@@ -99,12 +93,13 @@ static Result recover(const uint8_t* p, uint64_t n, uint32_t scope) {
     r.tail.clear();
     return r;
   }
-  put_fixed(r.tail, hs::recover_filetype(fh.filetype), 4);
-  put_fixed(r.tail, r.flags, 4);
-  put_fixed(r.tail, r.offset, 8);
-  put_fixed(r.tail, r.kept, 8);
-  put_fixed(r.tail, hs::kMagic, 8);
-  put_fixed(r.tail, crc32c(0, r.tail.data(), r.tail.size()), 4);
+  // the footer: its first 32 bytes, then the CRC of the rows extended over them
+  const size_t rows = r.tail.size();
+  r.tail.resize(rows + hs::kFooterSize);
+  uint8_t* ft = r.tail.data() + rows;
+  hsc::encode_footer(hs::recover_filetype(fh.filetype), r.flags, r.offset, r.kept, ft);
+  const uint32_t c = crc32c(0, r.tail.data(), rows + hsc::kFooterCrcBytes);
+  for (uint32_t i = 0; i < 4; i++) ft[hsc::kFooterCrcBytes + i] = (uint8_t)(c >> (8 * i));
   return r;
 }
 

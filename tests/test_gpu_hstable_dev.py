@@ -4,11 +4,13 @@ include/kdb_hstable_dev.h).
 Expected bytes come from the reference's own files (hstable_streams.npz) and
 from the host writer (csrc/hstable.cc), which tests/test_write_path.py pins to
 the reference and the oracle.  The cut edges are fed as synthetic per-entry
-arrays to both writers; kdb_index_load_files, which shares no code with the
-device writer but the CRC tables, then loads what the writer left in device
+arrays to both writers; kdb_index_load_files, which shares the CRC primitives
+and the format constants with the device writer but verifies footers and
+parses rows with code of its own, then loads what the writer left in device
 memory.
 """
 import os
+import struct
 import sys
 
 import numpy as np
@@ -284,6 +286,90 @@ def test_long_offset_array(gpu):
     want = host_files(batches, hs)
     assert len(want) == 1 and len(next(iter(want.values()))) > HEADER + 8192 * 26 + 80000
     assert_same_files(device_files(batches, hs), want)
+
+
+def real_batch(orc, rng, n):
+    """n entries of 26 to 298 bytes (the first has 26) that a recovery walk
+    accepts: a header by oracle.entry_header, a key of 1 to 8 bytes and a raw
+    value, kEntryFull; the rows' hashes are the headers'."""
+    hashes = rng.integers(0, 2 ** 64, n, dtype=np.uint64)
+    ents = []
+    for i in range(n):
+        key = bytes(rng.integers(0, 256, 1 + i % 8, dtype=np.uint8))
+        value = bytes(rng.integers(0, 256, int(rng.integers(0, 265)) if i else 0, dtype=np.uint8))
+        h = orc.entry_header(orc.crc32c(key + value), 0x8, len(key), len(value), 0, 0, int(hashes[i]))
+        ents.append(h + key + value)
+    assert len(ents[0]) == 26 and all(26 <= len(e) <= 300 for e in ents)
+    b = Batch([len(e) for e in ents], hashes=hashes, rng=rng)
+    b.entries = np.frombuffer(b"".join(ents), np.uint8).copy()
+    return b
+
+
+def rows_of(f):
+    """(offset_indexes, bytes of the rows, num_entries) of a closed file."""
+    oi, n = struct.unpack_from("<QQ", f, len(f) - 28)
+    return oi, len(f) - 36 - oi, n
+
+
+def test_short_offset_arrays(gpu, orc):
+    """The short end of the closer's arithmetic (csrc/hstable_close.h: 64 pieces
+    per file, crc::extend_block's 16 parts per piece), which the writer, the
+    index load and recovery share: files of 1, 2, 5, 7, 70 and 110 rows -- one
+    row; fewer than 64 bytes of rows, so some pieces are empty; just above 64,
+    where a piece has two bytes; below and above 1 024, where a wave's part
+    has two -- and five files of one entry each closed by one append
+    (hstable_size 8193, the smallest either writer takes: above the header
+    block, so the first entry already passes it).  Every
+    file equals the host writer's, loads into the index where it lies, and,
+    cut at its offset array, is recovered as the model recovers it."""
+    import recover_model as R
+    from kingdb_amd import put
+    from kingdb_amd import recover as rec
+    from kingdb_amd.index import HSTableIndex
+    rng = np.random.default_rng(67)
+    counts = (1, 2, 5, 7, 70, 110)
+    sets = [(real_batch(orc, rng, n), 1 << 20, 1) for n in counts] + [(real_batch(orc, rng, 5), 8193, 5)]
+    want = {}
+    for s, (b, hs, nfiles) in enumerate(sets):
+        host = host_files([b], hs)
+        assert len(host) == nfiles
+        want.update({"%d-%s" % (s, f): data for f, data in host.items()})
+    assert len(want) == 11
+    rb = [rows_of(want["%d-00000001" % s])[1] for s in range(6)]
+    print("row bytes", rb, [rows_of(f)[1] for n, f in sorted(want.items()) if n.startswith("6-")])
+    assert [rows_of(want["%d-00000001" % s])[2] for s in range(6)] == list(counts)
+    assert 3 <= rb[0] <= 15 and rb[0] < rb[1] < rb[2] < 64 < rb[3] <= 128 and rb[3] < rb[4] < 1024 < rb[5]
+    assert all(rows_of(f)[2] == 1 and rows_of(f)[1] <= 15 for n, f in want.items() if n.startswith("6-"))
+    # a, b: the device writer's files, and the index over them where they lie
+    got = {}
+    for s, (b, hs, nfiles) in enumerate(sets):
+        w = put.DeviceHSTableWriter(hs, 1, put.DeviceHSTableWriter.arena_bytes(hs, int(b.len.sum()), b.n))
+        try:
+            feed(w, b)
+            w.close()
+            files = w.files()
+            got.update({"%d-%s" % (s, f): data for f, data in files.items()})
+            ix = HSTableIndex.from_resident(w)
+            try:
+                assert ix.file_status == {f: 0 for f in files} and len(files) == nfiles, s
+                assert ix.entries == b.n, s
+            finally:
+                ix.close()
+        finally:
+            w.free()
+    assert_same_files(got, want)
+    # c: the files without offset array and footer, recovered in one call
+    torn = {n: f[:rows_of(f)[0]] for n, f in got.items()}
+    out, rep = rec.recover_files(torn)
+    assert sorted(out) == sorted(torn)
+    for n, f in torn.items():
+        st, model, mrep = R.recover(f, orc, "reference")
+        r = rep[n]
+        assert st == 0 and r.status == 0, n
+        assert out[n] == model, n
+        assert (r.entries_walked, r.rows_kept, r.entries_invalid, r.offset, r.footer_flags) == \
+            (mrep["walked"], mrep["kept"], mrep["invalid"], mrep["offset"], mrep["flags"]), n
+        assert model == want[n], n                     # the entries are whole: recovery gives the file back
 
 
 # ------------------------------------------------------------- 7: refusals

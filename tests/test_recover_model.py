@@ -8,10 +8,12 @@
     it may serve as the checker for the files the GPU tests build;
   * in `content` scope every multipart entry whose bytes are undamaged is
     kept, and the flipped ones are dropped;
-  * csrc/hstable_recover.h -- the step, the CRC range and the walk -- compiled
-    for the host into a stand-alone program under AddressSanitizer and UBSan,
-    over every fixture input in both scopes: a clean run whose every line
-    equals the model;
+  * csrc/hstable_recover.h -- the step, the CRC range and the walk -- and
+    csrc/hstable_close.h -- the rows and the footer, the encoders the writer's
+    and recovery's kernels call -- compiled for the host into a stand-alone
+    program under AddressSanitizer and UBSan, over every fixture input in both
+    scopes: a clean run whose every line (the CRC32C of the whole recovered
+    file among its fields) equals the model;
   * libkdb_lz4.so exports every symbol of include/kdb_recover.h.
 """
 import os
