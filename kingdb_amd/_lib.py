@@ -91,6 +91,9 @@ SIGNATURES = {
     "kdb_index_scan_sort_steps": (_i, [_vp, _c.POINTER(_u32)]),
     "kdb_index_scan_scratch_bytes": (_u64, [_u32]),
     "kdb_index_scan_batch": (_i, [_vp, _vp, _u64, _u32, _u64, _vp, _u64, _vp, _u64, _vp, _vp] + [_vp] * 10),
+    # include/kdb_index_add.h (newly closed files added to a loaded index)
+    "kdb_index_add_files": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _c.POINTER(_u64)]),
+    "kdb_index_add_stats": (_i, [_vp, _c.POINTER(_u32), _c.POINTER(_u64), _c.POINTER(_u64)]),
     "kdb_hstable_db_options": (_i, [_u64, _u32, _vp]),
     "kdb_hstable_writer_create": (_i, [_u64, _u32, _c.POINTER(_vp)]),
     "kdb_hstable_writer_create2": (_i, [_u64, _u32, _u32, _c.POINTER(_vp)]),

@@ -27,6 +27,10 @@
 //                        row region) and assembles the value
 //   index_hist_kernel / scan / index_fill_kernel
 //                        CSR buckets over hash & (B - 1), B a power of two >= 2 x rows
+// Add (include/kdb_index_add.h; StorageEngine::ProcessingLoopIndex,
+// storage/storage_engine.h:298-372; synchronous; the load is an add to an
+// empty handle): the kernels above over the new files alone, their rows
+// appended to the row arrays, then hist / scan / fill over all resident rows
 // Lookup (stream-ordered):
 //   index_get_kernel     wave per key: hash, bucket scan, candidates in
 //                        descending sequence number, header decode + checks
@@ -683,6 +687,17 @@ struct kdb_index {
   uint32_t* d_file_rank = nullptr;       // file slot -> rank in (timestamp, fileid) order
   uint32_t* d_rank_file = nullptr;       // and back
   std::vector<uint32_t> fileid;
+  // what kdb_index_add_files extends: host copies of the per-file arrays, the
+  // loaded files' timestamps (the order rule), and the rows the row arrays
+  // have room for (they grow geometrically)
+  std::vector<uint64_t> file_off, file_size, timestamp;
+  std::vector<int32_t> status;
+  std::vector<uint32_t> rank, rank_file;
+  uint32_t nloaded = 0;                  // files of status 0: the ranks in use
+  uint64_t row_cap = 0;
+  // kdb_index_add_stats
+  bool add_done = false;
+  uint64_t add_rows_parsed = 0;
   // the scan's live list (kdb_index_scan_prepare): rank << 32 | offset in
   // iterator order, and the exclusive sum of the live keys' lengths (live + 1
   // entries, on the device for the emit and on the host for the window checks)
@@ -727,10 +742,22 @@ void index_release(kdb_index* ix) {
   ix->nfiles = 0;
   ix->nrows = ix->nbuckets = 0;
   ix->fileid.clear();
+  ix->file_off.clear();
+  ix->file_size.clear();
+  ix->timestamp.clear();
+  ix->status.clear();
+  ix->rank.clear();
+  ix->rank_file.clear();
+  ix->nloaded = 0;
+  ix->row_cap = 0;
+  ix->add_done = false;
+  ix->add_rows_parsed = 0;
 }
 
-// Temporaries of one load, freed on every way out.
-struct LoadTemps {
+// Temporaries of one add, and what it builds beside the handle: the new
+// arrays are swapped into the handle at the very end, so after a successful
+// add these hold what the handle held before.  All freed on every way out.
+struct AddTemps {
   FileRec* d_rec = nullptr;
   ParseFile* d_pf = nullptr;
   uint32_t* d_tile_file = nullptr;
@@ -738,7 +765,17 @@ struct LoadTemps {
   uint64_t* d_tile_prefix = nullptr;
   uint32_t* d_malformed = nullptr;
   uint32_t* d_count = nullptr;
-  ~LoadTemps() {
+  uint64_t* d_file_off = nullptr;
+  uint64_t* d_file_size = nullptr;
+  uint32_t* d_fileid = nullptr;
+  uint32_t* d_file_rank = nullptr;
+  uint32_t* d_rank_file = nullptr;
+  uint64_t* d_start = nullptr;
+  Slot* d_slots = nullptr;
+  uint64_t* d_row_hash = nullptr;        // set only where the row arrays had to grow
+  uint32_t* d_row_off = nullptr;
+  uint32_t* d_row_file = nullptr;
+  ~AddTemps() {
     dfree(d_rec);
     dfree(d_pf);
     dfree(d_tile_file);
@@ -746,6 +783,16 @@ struct LoadTemps {
     dfree(d_tile_prefix);
     dfree(d_malformed);
     dfree(d_count);
+    dfree(d_file_off);
+    dfree(d_file_size);
+    dfree(d_fileid);
+    dfree(d_file_rank);
+    dfree(d_rank_file);
+    dfree(d_start);
+    dfree(d_slots);
+    dfree(d_row_hash);
+    dfree(d_row_off);
+    dfree(d_row_file);
   }
 };
 
@@ -756,36 +803,52 @@ hipError_t upload(hipStream_t st, T** d, const T* h, size_t n) {
   return hipSuccess;
 }
 
-hipError_t index_load(kdb_index* ix, hipStream_t st, const uint8_t* d_files, const uint64_t* file_off,
-                      const uint64_t* file_size, const uint32_t* fileid, uint32_t nfiles, int32_t* file_status,
-                      bool* too_many) {
-  LoadTemps t;
-  ix->d_files = d_files;
-  ix->nfiles = nfiles;
-  ix->fileid.assign(fileid, fileid + nfiles);
-  KDB_TRY(upload(st, &ix->d_file_off, file_off, nfiles));
-  KDB_TRY(upload(st, &ix->d_file_size, file_size, nfiles));
-  KDB_TRY(upload(st, &ix->d_fileid, fileid, nfiles));
-  std::vector<FileRec> rec(nfiles);
-  if (nfiles) {
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_rec), nfiles * sizeof(FileRec)));
-    hipLaunchKernelGGL(index_file_kernel, dim3(nfiles), dim3(kFileBlock), 0, st, d_files, ix->d_file_off,
-                       ix->d_file_size, t.d_rec);
+enum class Refused { kNo, kTooMany, kOrder };
+
+// The one way rows get into a handle.  The handle holds nfiles files (none:
+// the add is the load); the host arrays describe the nadd new ones, all in
+// ix->d_files.  The handle changes only at the end, in the swap.
+hipError_t index_add(kdb_index* ix, hipStream_t st, const uint64_t* file_off, const uint64_t* file_size,
+                     const uint32_t* fileid, uint32_t nadd, int32_t* file_status, uint64_t* rows_added,
+                     Refused* refused) {
+  const uint8_t* d_files = ix->d_files;
+  const uint32_t nf0 = ix->nfiles, nf = nf0 + nadd;
+  const uint64_t nrows0 = ix->nrows;
+  // host arrays first, the device temporaries after them: hipFree waits for
+  // the copies that read these vectors before they go out of scope
+  std::vector<uint64_t> h_off(ix->file_off), h_size(ix->file_size), h_ts(ix->timestamp);
+  std::vector<uint32_t> h_id(ix->fileid), rank(ix->rank), rank_file(ix->rank_file);
+  std::vector<int32_t> h_status(ix->status);
+  std::vector<FileRec> rec(nadd);
+  std::vector<int32_t> status(nadd);
+  std::vector<uint32_t> order, tile_file, bad(nf);
+  std::vector<ParseFile> pf;
+  AddTemps t;
+  h_off.insert(h_off.end(), file_off, file_off + nadd);
+  h_size.insert(h_size.end(), file_size, file_size + nadd);
+  h_id.insert(h_id.end(), fileid, fileid + nadd);
+  KDB_TRY(upload(st, &t.d_file_off, h_off.data(), nf));
+  KDB_TRY(upload(st, &t.d_file_size, h_size.data(), nf));
+  KDB_TRY(upload(st, &t.d_fileid, h_id.data(), nf));
+  if (nadd) {
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_rec), nadd * sizeof(FileRec)));
+    hipLaunchKernelGGL(index_file_kernel, dim3(nadd), dim3(kFileBlock), 0, st, d_files, t.d_file_off + nf0,
+                       t.d_file_size + nf0, t.d_rec);
     KDB_TRY(hipGetLastError());
-    KDB_TRY(hipMemcpyAsync(rec.data(), t.d_rec, nfiles * sizeof(FileRec), hipMemcpyDeviceToHost, st));
+    KDB_TRY(hipMemcpyAsync(rec.data(), t.d_rec, nadd * sizeof(FileRec), hipMemcpyDeviceToHost, st));
   }
   KDB_TRY(hipStreamSynchronize(st));
-  std::vector<int32_t> status(nfiles);
-  for (uint32_t f = 0; f < nfiles; f++) status[f] = rec[f].status;
+  for (uint32_t f = 0; f < nadd; f++) status[f] = rec[f].status;
 
-  // LoadDatabase's order (:1007-1014): by (timestamp, fileid)
-  std::vector<uint32_t> order;
-  std::vector<ParseFile> pf;
-  std::vector<uint32_t> tile_file;
-  uint64_t nrows = 0;
+  // LoadDatabase's order (:1007-1014): by (timestamp, fileid), the new files
+  // among themselves; their rows are numbered after the rows the handle holds
+  uint64_t* row_hash = ix->d_row_hash;
+  uint32_t* row_off = ix->d_row_off;
+  uint32_t* row_file = ix->d_row_file;
+  uint64_t row_cap = ix->row_cap, rows_new = 0, rows_parsed = 0;
   for (;;) {
     order.clear();
-    for (uint32_t f = 0; f < nfiles; f++)
+    for (uint32_t f = 0; f < nadd; f++)
       if (status[f] == 0) order.push_back(f);
     std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
       if (rec[a].timestamp != rec[b].timestamp) return rec[a].timestamp < rec[b].timestamp;
@@ -793,92 +856,153 @@ hipError_t index_load(kdb_index* ix, hipStream_t st, const uint8_t* d_files, con
     });
     pf.clear();
     tile_file.clear();
-    nrows = 0;
+    rows_new = 0;
     for (uint32_t f : order) {
       ParseFile p{};
       p.reg_off = file_off[f] + rec[f].offset_indexes;
       p.reg_len = file_size[f] - hs::kFooterSize - rec[f].offset_indexes;
       p.nvar = 2u * rec[f].num_entries;
-      p.row_base = nrows;
+      p.row_base = nrows0 + rows_new;
       p.first_tile = (uint32_t)tile_file.size();
       p.ntiles = (uint32_t)((p.reg_len + kParseTile - 1u) / kParseTile);
-      p.slot = f;
-      nrows += rec[f].num_entries;
-      if (nrows > kMaxRows || tile_file.size() + p.ntiles > 0x7FFFFFFFull) {
-        *too_many = true;
+      p.slot = nf0 + f;
+      rows_new += rec[f].num_entries;
+      if (nrows0 + rows_new > kMaxRows || tile_file.size() + p.ntiles > 0x7FFFFFFFull) {
+        *refused = Refused::kTooMany;
         return hipSuccess;
       }
       tile_file.insert(tile_file.end(), p.ntiles, (uint32_t)pf.size());
       pf.push_back(p);
     }
-    dfree(ix->d_row_hash);
-    dfree(ix->d_row_off);
-    dfree(ix->d_row_file);
     dfree(t.d_pf);
     dfree(t.d_tile_file);
     dfree(t.d_tile_count);
     dfree(t.d_tile_prefix);
     dfree(t.d_malformed);
     const uint32_t ntiles = (uint32_t)tile_file.size();
-    if (nrows == 0 || ntiles == 0) break;
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&ix->d_row_hash), nrows * 8u));
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&ix->d_row_off), nrows * 4u));
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&ix->d_row_file), nrows * 4u));
+    if (rows_new == 0 || ntiles == 0) break;
+    if (nrows0 + rows_new > row_cap) {
+      // the row arrays grow geometrically (a load sizes them exactly); the
+      // handle keeps its own until the swap.  Later passes number fewer rows.
+      row_cap = std::max(nrows0 + rows_new, std::min(2u * row_cap, kMaxRows));
+      KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_row_hash), row_cap * 8u));
+      KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_row_off), row_cap * 4u));
+      KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_row_file), row_cap * 4u));
+      if (nrows0) {
+        KDB_TRY(hipMemcpyAsync(t.d_row_hash, ix->d_row_hash, nrows0 * 8u, hipMemcpyDeviceToDevice, st));
+        KDB_TRY(hipMemcpyAsync(t.d_row_off, ix->d_row_off, nrows0 * 4u, hipMemcpyDeviceToDevice, st));
+        KDB_TRY(hipMemcpyAsync(t.d_row_file, ix->d_row_file, nrows0 * 4u, hipMemcpyDeviceToDevice, st));
+      }
+      row_hash = t.d_row_hash;
+      row_off = t.d_row_off;
+      row_file = t.d_row_file;
+    }
     KDB_TRY(upload(st, &t.d_pf, pf.data(), pf.size()));
     KDB_TRY(upload(st, &t.d_tile_file, tile_file.data(), tile_file.size()));
     KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_tile_count), (size_t)ntiles * 4u));
     KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_tile_prefix), ((size_t)ntiles + 1u) * 8u));
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_malformed), (size_t)nfiles * 4u));
-    KDB_TRY(hipMemsetAsync(t.d_malformed, 0, (size_t)nfiles * 4u, st));
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_malformed), (size_t)nf * 4u));
+    KDB_TRY(hipMemsetAsync(t.d_malformed, 0, (size_t)nf * 4u, st));
     hipLaunchKernelGGL(index_count_kernel, dim3(ntiles), dim3(kParseTile), 0, st, d_files, t.d_pf, t.d_tile_file,
                        t.d_tile_count);
     KDB_TRY(hipGetLastError());
     KDB_TRY(launch_exclusive_scan(st, t.d_tile_count, ntiles, t.d_tile_prefix, t.d_tile_prefix + ntiles));
+    // rows [nrows0, nrows0 + rows_new): beyond what the handle's lookups read
     hipLaunchKernelGGL(index_parse_kernel, dim3(ntiles), dim3(kParseTile), 0, st, d_files, t.d_pf, t.d_tile_file,
-                       t.d_tile_prefix, ix->d_row_hash, ix->d_row_off, ix->d_row_file, t.d_malformed);
+                       t.d_tile_prefix, row_hash, row_off, row_file, t.d_malformed);
     KDB_TRY(hipGetLastError());
-    std::vector<uint32_t> bad(nfiles);
-    KDB_TRY(hipMemcpyAsync(bad.data(), t.d_malformed, (size_t)nfiles * 4u, hipMemcpyDeviceToHost, st));
+    rows_parsed += rows_new;
+    KDB_TRY(hipMemcpyAsync(bad.data(), t.d_malformed, (size_t)nf * 4u, hipMemcpyDeviceToHost, st));
     KDB_TRY(hipStreamSynchronize(st));
     bool again = false;
-    for (uint32_t f = 0; f < nfiles; f++)
-      if (bad[f] && status[f] == 0) {
+    for (uint32_t f = 0; f < nadd; f++)
+      if (bad[nf0 + f] && status[f] == 0) {
         status[f] = -3;       // no row of a malformed array is kept: number the rows again without it
         again = true;
       }
     if (!again) break;
   }
-  for (uint32_t f = 0; f < nfiles; f++) file_status[f] = status[f];
-  {
-    // the scan orders by the file's rank; a file that did not load has no rows and no rank
-    std::vector<uint32_t> rank(nfiles, 0xFFFFFFFFu), rank_file(nfiles, 0u);
-    for (uint32_t i = 0; i < order.size(); i++) {
-      rank[order[i]] = i;
-      rank_file[i] = order[i];
-    }
-    KDB_TRY(upload(st, &ix->d_file_rank, rank.data(), nfiles));
-    KDB_TRY(upload(st, &ix->d_rank_file, rank_file.data(), nfiles));
-    KDB_TRY(hipStreamSynchronize(st));     // the vectors go out of scope
-  }
-  ix->nrows = nrows;
-  if (nrows == 0) return hipSuccess;
+  // a fresh load of all the files numbers the new rows after the loaded ones
+  // only if every new file sorts after every loaded one
+  for (uint32_t f : order)
+    for (uint32_t o = 0; o < nf0; o++)
+      if (h_status[o] == 0 && (rec[f].timestamp < h_ts[o] || (rec[f].timestamp == h_ts[o] && fileid[f] <= h_id[o]))) {
+        status[f] = KDB_INDEX_FILE_ORDER;
+        *refused = Refused::kOrder;
+        break;
+      }
+  for (uint32_t f = 0; f < nadd; f++) file_status[f] = status[f];
+  if (*refused != Refused::kNo) return hipSuccess;
 
-  uint64_t B = 2;
-  while (B < 2u * nrows) B <<= 1;
+  // the scan orders by the file's rank; a file that did not load has no rows and no rank
+  rank.resize(nf, 0xFFFFFFFFu);
+  rank_file.resize(nf, 0u);
+  for (uint32_t i = 0; i < order.size(); i++) {
+    rank[nf0 + order[i]] = ix->nloaded + i;
+    rank_file[ix->nloaded + i] = nf0 + order[i];
+  }
+  KDB_TRY(upload(st, &t.d_file_rank, rank.data(), nf));
+  KDB_TRY(upload(st, &t.d_rank_file, rank_file.data(), nf));
+
+  const uint64_t nrows = nrows0 + rows_new;
+  uint64_t B = ix->nbuckets;
+  if (rows_new) {
+    // the buckets are built again from all resident rows, as a load builds
+    // them, whether B doubles or stays: moving the old slots and placing only
+    // the new rows was measured and not kept
+    B = 2;
+    while (B < 2u * nrows) B <<= 1;
+    const uint32_t n = (uint32_t)nrows;
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_start), (B + 1u) * 8u));
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_slots), nrows * sizeof(Slot)));
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_count), B * 4u));
+    KDB_TRY(hipMemsetAsync(t.d_count, 0, B * 4u, st));
+    const uint32_t g = std::min<uint32_t>((n + 255u) / 256u, 2048u);
+    hipLaunchKernelGGL(index_hist_kernel, dim3(g), dim3(256), 0, st, row_hash, n, B - 1u, t.d_count);
+    KDB_TRY(hipGetLastError());
+    KDB_TRY(launch_exclusive_scan(st, t.d_count, (uint32_t)B, t.d_start, t.d_start + B));
+    hipLaunchKernelGGL(index_fill_kernel, dim3(g), dim3(256), 0, st, row_hash, row_off, row_file, n, B - 1u,
+                       t.d_start, t.d_count, t.d_slots);
+    KDB_TRY(hipGetLastError());
+  }
+  for (uint32_t f = 0; f < nadd; f++) {
+    h_ts.push_back(rec[f].timestamp);
+    h_status.push_back(status[f]);
+  }
+  KDB_TRY(hipStreamSynchronize(st));
+
+  // nothing can fail any more: the handle takes what was built, `t` what it held
+  std::swap(ix->d_file_off, t.d_file_off);
+  std::swap(ix->d_file_size, t.d_file_size);
+  std::swap(ix->d_fileid, t.d_fileid);
+  std::swap(ix->d_file_rank, t.d_file_rank);
+  std::swap(ix->d_rank_file, t.d_rank_file);
+  if (rows_new) {
+    std::swap(ix->d_start, t.d_start);
+    std::swap(ix->d_slots, t.d_slots);
+  }
+  if (t.d_row_hash) {
+    std::swap(ix->d_row_hash, t.d_row_hash);
+    std::swap(ix->d_row_off, t.d_row_off);
+    std::swap(ix->d_row_file, t.d_row_file);
+    ix->row_cap = row_cap;
+  }
+  ix->file_off.swap(h_off);
+  ix->file_size.swap(h_size);
+  ix->fileid.swap(h_id);
+  ix->timestamp.swap(h_ts);
+  ix->status.swap(h_status);
+  ix->rank.swap(rank);
+  ix->rank_file.swap(rank_file);
+  ix->nloaded += (uint32_t)order.size();
+  ix->nfiles = nf;
+  ix->nrows = nrows;
   ix->nbuckets = B;
-  const uint32_t n = (uint32_t)nrows;
-  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&ix->d_start), (B + 1u) * 8u));
-  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&ix->d_slots), nrows * sizeof(Slot)));
-  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_count), B * 4u));
-  KDB_TRY(hipMemsetAsync(t.d_count, 0, B * 4u, st));
-  const uint32_t g = std::min<uint32_t>((n + 255u) / 256u, 2048u);
-  hipLaunchKernelGGL(index_hist_kernel, dim3(g), dim3(256), 0, st, ix->d_row_hash, n, B - 1u, t.d_count);
-  KDB_TRY(hipGetLastError());
-  KDB_TRY(launch_exclusive_scan(st, t.d_count, (uint32_t)B, ix->d_start, ix->d_start + B));
-  hipLaunchKernelGGL(index_fill_kernel, dim3(g), dim3(256), 0, st, ix->d_row_hash, ix->d_row_off, ix->d_row_file, n,
-                     B - 1u, ix->d_start, t.d_count, ix->d_slots);
-  KDB_TRY(hipGetLastError());
-  return hipStreamSynchronize(st);
+  scan_release(ix);
+  ix->add_done = true;
+  ix->add_rows_parsed = rows_parsed;
+  *rows_added = rows_new;
+  return hipSuccess;
 }
 
 }  // namespace
@@ -908,14 +1032,50 @@ extern "C" int kdb_index_load_files(kdb_index* ix, void* stream, const uint8_t* 
   for (uint32_t f = 0; f < nfiles; f++)
     if (file_size[f] > hs::kMaxFileSize) return KDB_PUT_EINVAL;
   index_release(ix);
-  bool too_many = false;
-  const hipError_t e = index_load(ix, (hipStream_t)stream, d_files, file_off, file_size, fileid, nfiles,
-                                  file_status_out, &too_many);
-  if (e != hipSuccess || too_many) {
+  ix->d_files = d_files;
+  Refused refused = Refused::kNo;
+  uint64_t added = 0;
+  const hipError_t e = index_add(ix, (hipStream_t)stream, file_off, file_size, fileid, nfiles, file_status_out,
+                                 &added, &refused);
+  if (e != hipSuccess || refused != Refused::kNo) {
     index_release(ix);
-    return too_many ? KDB_PUT_EINVAL : hip_code(e);
+    return e != hipSuccess ? hip_code(e) : KDB_PUT_EINVAL;
   }
+  ix->add_done = false;                  // kdb_index_add_stats speaks of adds
   if (entries_out) *entries_out = ix->nrows;
+  return KDB_PUT_OK;
+}
+
+extern "C" int kdb_index_add_files(kdb_index* ix, void* stream, const uint8_t* d_files, const uint64_t* file_off,
+                                   const uint64_t* file_size, const uint32_t* fileid, uint32_t nadd, uint32_t flags,
+                                   int32_t* file_status_out, uint64_t* entries_added_out) {
+  if (!ix || (flags & ~KDB_INDEX_ADD_REBUILD) ||
+      (nadd && (!d_files || !file_off || !file_size || !fileid || !file_status_out)))
+    return KDB_PUT_EINVAL;
+  if (entries_added_out) *entries_added_out = 0;
+  if (nadd == 0) return KDB_PUT_OK;
+  if (nadd > 0xFFFFFFFFu - ix->nfiles || (ix->nfiles && d_files != ix->d_files)) return KDB_PUT_EINVAL;
+  for (uint32_t f = 0; f < nadd; f++)
+    if (file_size[f] > hs::kMaxFileSize) return KDB_PUT_EINVAL;
+  const uint8_t* held = ix->d_files;
+  ix->d_files = d_files;                 // a handle without files adopts the buffer
+  Refused refused = Refused::kNo;
+  uint64_t added = 0;
+  const hipError_t e = index_add(ix, (hipStream_t)stream, file_off, file_size, fileid, nadd, file_status_out,
+                                 &added, &refused);
+  if (e != hipSuccess || refused != Refused::kNo) {
+    ix->d_files = held;
+    return e != hipSuccess ? hip_code(e) : KDB_PUT_EINVAL;
+  }
+  if (entries_added_out) *entries_added_out = added;
+  return KDB_PUT_OK;
+}
+
+extern "C" int kdb_index_add_stats(const kdb_index* ix, uint32_t* merged, uint64_t* nbuckets, uint64_t* rows_parsed) {
+  if (!ix || !ix->add_done) return KDB_PUT_EINVAL;
+  if (merged) *merged = 0u;                // the buckets are always rebuilt
+  if (nbuckets) *nbuckets = ix->nbuckets;
+  if (rows_parsed) *rows_parsed = ix->add_rows_parsed;
   return KDB_PUT_OK;
 }
 

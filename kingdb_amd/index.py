@@ -16,6 +16,12 @@ set of closed HSTable files and the batched lookup in front of the decoder.
   HSTableIndex.from_resident(writer)
                           an index over the files a put.DeviceHSTableWriter
                           holds in device memory, with no upload
+  .refresh()              adds the files the writer has closed since
+                          (kdb_index_add_files; StorageEngine::ProcessingLoopIndex):
+                          write -> refresh -> get, with no file loaded twice
+  HSTableIndex(files, reserve=N) / .add_files(files)
+                          the same for an uploaded index: new files go into
+                          the N spare bytes behind the first ones
 
 status: 0 OK, NOTFOUND, DELETED (Database::Get reports NotFound), MULTIPART
 (MultipartRequired), or the decoder's -1 / -2 (see get.py).  Databases opened
@@ -36,6 +42,7 @@ from . import _lib
 from .lz4 import DeviceBuffer, Stream
 
 NOTFOUND, DELETED, MULTIPART = -3, -4, -5
+FILE_ORDER = -4                  # file status KDB_INDEX_FILE_ORDER: not newer than the loaded files
 MULTIPART_REQUIRED = 1 << 20     # internal__size_multipart_required
 
 
@@ -87,8 +94,10 @@ class _Borrowed:
 
 class HSTableIndex:
     def __init__(self, files: dict[str, bytes], hash_type: int = 1, stream: Stream | None = None,
-                 recover: str | None = None):
+                 recover: str | None = None, reserve: int = 0):
         from . import recover as rec
+        if reserve < 0:
+            raise ValueError("reserve is a byte count")
         if recover is not None:
             rec.scope_code(recover)
         self.names = sorted(files)
@@ -108,6 +117,8 @@ class HSTableIndex:
         self.files = None
         self.h = None
         self._scan = None                # (verify, live, key bytes, max key length) of the prepared scan
+        self._owner = None               # from_resident: the writer whose arena the index borrows
+        self._reserve = reserve          # spare bytes behind the uploaded files, for add_files
         st = stream.ptr if stream else None
         self._upload(files, size, cap, st)
         h = ctypes.c_void_p()
@@ -145,8 +156,9 @@ class HSTableIndex:
         self.file_off, self.file_size = off, size.copy()
         if self.files is not None:
             self.files.free()
-        self.files = DeviceBuffer(total + 64)
+        self.files = DeviceBuffer(total + self._reserve + 64)
         self.files.upload(buf, stream=st)
+        self._used = total               # add_files puts the next file behind this
 
     def _load(self, st) -> np.ndarray:
         n = len(self.names)
@@ -175,6 +187,7 @@ class HSTableIndex:
         self.file_off, self.file_size, self.fileid = off.copy(), size.copy(), fid.copy()
         self.files = _Borrowed(ptr, writer.arena)
         self._owner = writer
+        self._reserve = self._used = 0
         self.recovered = {}
         self.h = None
         self._scan = None
@@ -191,6 +204,90 @@ class HSTableIndex:
         self.file_status = {f: int(s) for f, s in zip(self.names, status[:n])}
         self.entries = entries.value
         return self
+
+    def _add(self, st, off: np.ndarray, size: np.ndarray, fid: np.ndarray, flags: int = 0) -> dict[str, int]:
+        """kdb_index_add_files of files already resident in self.files: their
+        statuses by name.  The index changes only if the call succeeds."""
+        n = len(fid)
+        off, size, fid = (np.ascontiguousarray(off, np.uint64), np.ascontiguousarray(size, np.uint64),
+                          np.ascontiguousarray(fid, np.uint32))
+        status = np.zeros(max(n, 1), np.int32)
+        added = ctypes.c_uint64(0)
+        rc = lib().kdb_index_add_files(self.h, st, self.files.ptr, off.ctypes.data, size.ctypes.data, fid.ctypes.data,
+                                       n, flags, status.ctypes.data, ctypes.byref(added))
+        names = ["%08x" % int(f) for f in fid]
+        if rc != _lib.OK:
+            refused = [f for f, s in zip(names, status[:n]) if s == FILE_ORDER]
+            _lib.check(rc, "kdb_index_add_files" + (f" (not newer than the loaded files: {refused})" if refused else ""))
+        self._scan = None
+        self.names += names
+        self.file_off = np.concatenate([self.file_off, off])
+        self.file_size = np.concatenate([self.file_size, size])
+        self.fileid = np.concatenate([self.fileid, fid])
+        res = {f: int(s) for f, s in zip(names, status[:n])}
+        self.file_status.update(res)
+        self.entries += added.value
+        return res
+
+    def refresh(self, stream: Stream | None = None) -> int:
+        """For an index made by from_resident(): adds the files its writer has
+        closed since the index last looked (kdb_index_add_files, the part of
+        StorageEngine::ProcessingLoopIndex a flush triggers) and returns the
+        rows added.  Files already held are not read again.  Entries of the
+        writer's still open file are not readable before it closes.  A
+        prepared scan is dropped (the next scan prepares again).  Not to run
+        concurrently with lookups on this index."""
+        if self._owner is None:
+            raise ValueError("refresh() is for an index made by from_resident(); use add_files()")
+        ptr, off, size, fid = self._owner.resident()
+        held = {int(f) for f in self.fileid}
+        new = [i for i in range(len(fid)) if int(fid[i]) not in held]
+        if not new:
+            return 0
+        before = self.entries
+        self._add(stream.ptr if stream else None, off[new], size[new], fid[new])
+        return self.entries - before
+
+    def add_files(self, files: dict[str, bytes], stream: Stream | None = None) -> dict[str, int]:
+        """Uploads `files` into the room HSTableIndex(..., reserve=) left behind
+        the files the index holds, at 64-byte-aligned offsets, and adds them
+        (kdb_index_add_files): their statuses by name, as `.file_status`.  The
+        files must be newer, by (timestamp, fileid), than every file held.
+        `recover=` is not applied: a file without a usable footer reports -1.
+        ValueError, before anything is uploaded, on a name already held or
+        files that do not fit the reserve; the index stays as it was."""
+        if self._owner is not None:
+            raise ValueError("add_files() is for an index that owns its buffer; use refresh()")
+        names = sorted(files)
+        dup = [f for f in names if f in self.names]
+        if dup:
+            raise ValueError(f"add_files: already held: {dup}")
+        if not names:
+            return {}
+        size = np.array([len(files[f]) for f in names], np.uint64)
+        start = (self._used + 63) & ~63
+        off = np.zeros(len(names), np.uint64)
+        off[1:] = np.cumsum((size[:-1] + np.uint64(63)) & ~np.uint64(63))
+        off += np.uint64(start)
+        end = int(off[-1] + size[-1])
+        if end + 64 > self.files.nbytes:
+            raise ValueError(f"add_files: {end - start} bytes do not fit the {self.files.nbytes - 64 - start} "
+                             "bytes left of the reserve")
+        buf = np.zeros(end - start + 64, np.uint8)
+        for f, o in zip(names, off):
+            buf[int(o) - start:int(o) - start + len(files[f])] = np.frombuffer(files[f], np.uint8)
+        st = stream.ptr if stream else None
+        self.files.upload(buf, start, stream=st)
+        res = self._add(st, off, size, np.array([int(f, 16) for f in names], np.uint32))
+        self._used = end
+        return res
+
+    def add_stats(self) -> tuple[int, int, int]:
+        """(merged, buckets, rows parsed) of the last add (kdb_index_add_stats)."""
+        m, b, r = ctypes.c_uint32(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _lib.check(lib().kdb_index_add_stats(self.h, ctypes.byref(m), ctypes.byref(b), ctypes.byref(r)),
+                   "kdb_index_add_stats")
+        return m.value, b.value, r.value
 
     def pairs(self) -> tuple[np.ndarray, np.ndarray]:
         """The loaded rows in sequence order: (hashed keys, fileid << 32 | offset)."""
