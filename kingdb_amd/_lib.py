@@ -76,6 +76,9 @@ SIGNATURES = {
     "kdb_put_scratch_bytes": (_u64, [_u32, _u32, _u64]),
     "kdb_put_entries_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _u64,
                                    _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # include/kdb_ops.h (puts and deletes in one batch): op, flags, then kdb_put_entries_batch's arguments
+    "kdb_put_ops_batch": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp,
+                               _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "kdb_get_scratch_bytes": (_u64, [_u32, _u64]),
     "kdb_get_values_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _i, _vp, _vp, _u64, _u32, _u32, _vp,
                                   _u64, _vp, _vp]),

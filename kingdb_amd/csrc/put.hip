@@ -34,6 +34,9 @@
 //   put_entry_kernel    wave per value, the rest: key + stored chunks copied into
 //                       place, CRC32C (64-lane chunked, GF(2) tree combine), key
 //                       hash, EntryHeader bytes
+// An item may be a delete (include/kdb_ops.h): the policy kernel lays out
+// Database::Delete's entry, a header of flags 0x9 and zeros followed by the
+// key, and the entry kernels write it in the place a put's entry would take.
 // The host (hstable.cc) then cuts the dense entry stream into HSTable files
 // and writes their headers and offset arrays.
 #include <hip/hip_runtime.h>
@@ -41,6 +44,7 @@
 #include <cstdint>
 
 #include "../../include/kdb_lz4.h"
+#include "../../include/kdb_ops.h"
 #include "crc_device.h"
 #include "hash_device.h"
 #include "lz4_device.h"
@@ -54,7 +58,7 @@ hipError_t launch_compress(bool frame, hipStream_t st, const uint8_t* src, const
 
 namespace {
 
-constexpr uint32_t kEntryFull = 0x8, kUncompacted = 0x2, kHasPadding = 0x4;   // format.h:34-42
+constexpr uint32_t kTypeDelete = 0x1, kEntryFull = 0x8, kUncompacted = 0x2, kHasPadding = 0x4;   // format.h:34-42
 
 // ----------------------------------------------------------------- CRC-8 of the header
 // crc32c::crc8 (crc32c.cc:439-475): reflected, polynomial 0xB2, pre/post xor 0xff.
@@ -136,8 +140,13 @@ __global__ void put_prep_kernel(const uint64_t* __restrict__ value_off, const ui
 }
 
 // Thread per value: Database::PutPartValidSize over the value's chunks, then
-// the HSTableManager view of the resulting orders.
-__global__ void put_policy_kernel(const uint32_t* __restrict__ key_len, const uint64_t* __restrict__ value_len,
+// the HSTableManager view of the resulting orders.  op (null: all puts) marks
+// the deletes: Database::Delete goes past PutPartValidSize (database.cc:279-286,
+// write_buffer.cc:149-152) and WriteFirstPartOrSmallOrder writes a header of
+// flags kTypeDelete | kEntryFull and zeros, then the key
+// (hstable_manager.h:694-710).
+__global__ void put_policy_kernel(const uint8_t* __restrict__ op, const uint32_t* __restrict__ key_len,
+                                  const uint64_t* __restrict__ value_len,
                                   const uint32_t* __restrict__ part_first, const uint32_t* __restrict__ chunk_len,
                                   const uint32_t* __restrict__ frame_len, const int32_t* __restrict__ fstatus,
                                   uint32_t n, uint64_t* __restrict__ occ, uint32_t* __restrict__ plen,
@@ -147,6 +156,23 @@ __global__ void put_policy_kernel(const uint32_t* __restrict__ key_len, const ui
     const uint64_t V = value_len[v];
     const uint64_t pad = padding_size(V);
     const uint32_t p0 = part_first[v], p1 = part_first[v + 1];
+    const uint32_t o8 = op ? op[v] : (uint32_t)KDB_OP_PUT;
+    if (o8 != KDB_OP_PUT) {
+      ValueLayout L{};
+      const uint32_t klen = key_len[v];
+      if (o8 != KDB_OP_DELETE || p1 != p0 || V != 0) {   // no such order: refused like a put that fails
+        L.status = -1;
+        lay[v] = L;
+        entry_len[v] = 0;
+        big[1u + atomicAdd(big, 1u)] = v;
+        continue;
+      }
+      L.flags = kEntryFull | kTypeDelete;
+      lay[v] = L;
+      entry_len[v] = header_len(L.flags, klen, 0, 0) + klen;
+      if (!small_entry(L, 0u, klen)) big[1u + atomicAdd(big, 1u)] = v;
+      continue;
+    }
     bool enabled = true;
     uint64_t ts_offset = 0, comp_total = 0, off = 0, svc = 0, crc_bytes = 0;
     int32_t status = 0;
@@ -324,9 +350,9 @@ __global__ __launch_bounds__(256) void put_entry_small_kernel(
     const uint8_t* __restrict__ keys, const uint64_t* __restrict__ key_off, const uint32_t* __restrict__ key_len,
     const uint64_t* __restrict__ value_len, const uint32_t* __restrict__ part_first, PartSrc src,
     const uint64_t* __restrict__ occ, const uint32_t* __restrict__ plen, const ValueLayout* __restrict__ lay,
-    uint32_t n, uint32_t hash_type, uint8_t* __restrict__ entries, const uint64_t* __restrict__ entry_off,
-    uint64_t* __restrict__ hashed, uint32_t* __restrict__ crc_out, uint32_t* __restrict__ kind_out,
-    int32_t* __restrict__ status_out) {
+    uint32_t n, uint32_t hash_type, uint32_t delete_hashed, uint8_t* __restrict__ entries,
+    const uint64_t* __restrict__ entry_off, uint64_t* __restrict__ hashed, uint32_t* __restrict__ crc_out,
+    uint32_t* __restrict__ kind_out, int32_t* __restrict__ status_out) {
   __shared__ uint32_t s_t[256];
   __shared__ uint32_t s4[1024];
   __shared__ uint8_t s_c8[256];
@@ -362,8 +388,12 @@ __global__ __launch_bounds__(256) void put_entry_small_kernel(
       }
       if (len > skip) c = crc_copy(cb, vd + skip, len - skip, c, s4, s_t);
     }
-    const uint32_t crc = c ^ 0xFFFFFFFFu;
+    // a delete order carries crc32 0, and the reference never assigns its
+    // header's hash (hstable_manager.h:694-702): 0 unless the caller asks
+    const bool del = (L.flags & kTypeDelete) != 0;
+    const uint32_t crc = del ? 0u : c ^ 0xFFFFFFFFu;
     const uint64_t h = hash_type == 1 ? xxh64(key, klen) : murmur3_64(key, klen);
+    const uint64_t hh = del && !delete_hashed ? 0u : h;
     hashed[v] = h;
     crc_out[v] = crc;
     // header bytes 1 .. hl-1 in order, each into the CRC-8, then byte 0
@@ -383,7 +413,7 @@ __global__ __launch_bounds__(256) void put_entry_small_kernel(
     emit_varint(V);
     for (int i = 0; i < 8; i++) emit((uint32_t)(L.svc_hdr >> (8 * i)) & 0xffu);
     emit_varint(L.pad_hdr);
-    for (int i = 0; i < 8; i++) emit((uint32_t)(h >> (8 * i)) & 0xffu);
+    for (int i = 0; i < 8; i++) emit((uint32_t)(hh >> (8 * i)) & 0xffu);
     dst[0] = (uint8_t)(c8 ^ 0xffu);
   }
 }
@@ -393,9 +423,10 @@ __global__ __launch_bounds__(kEntryBlock) void put_entry_kernel(
     const uint8_t* __restrict__ keys, const uint64_t* __restrict__ key_off, const uint32_t* __restrict__ key_len,
     const uint64_t* __restrict__ value_len, const uint32_t* __restrict__ part_first, PartSrc src,
     const uint64_t* __restrict__ occ, const uint32_t* __restrict__ plen, const ValueLayout* __restrict__ lay,
-    uint32_t n, uint32_t hash_type, uint8_t* __restrict__ entries, const uint64_t* __restrict__ entry_off,
-    const uint32_t* __restrict__ entry_len, uint64_t* __restrict__ hashed, uint32_t* __restrict__ crc_out,
-    uint32_t* __restrict__ kind_out, int32_t* __restrict__ status_out, const uint32_t* __restrict__ big) {
+    uint32_t n, uint32_t hash_type, uint32_t delete_hashed, uint8_t* __restrict__ entries,
+    const uint64_t* __restrict__ entry_off, const uint32_t* __restrict__ entry_len, uint64_t* __restrict__ hashed,
+    uint32_t* __restrict__ crc_out, uint32_t* __restrict__ kind_out, int32_t* __restrict__ status_out,
+    const uint32_t* __restrict__ big) {
   const uint32_t nbig = big[0];
   if (blockIdx.x * (kEntryBlock / 64) >= nbig) return;
   __shared__ uint32_t s_t[256];
@@ -435,10 +466,12 @@ __global__ __launch_bounds__(kEntryBlock) void put_entry_kernel(
 
     // CRC32C(key || every chunk_final) (database.cc:251-257), on the wave
     const PutMsg msg{key, klen, src, plen, p0, p1};
-    const uint32_t crc = crc::extend_wave(0u, (uint64_t)klen + L.crc_bytes, msg, s_t);
+    const bool del = (L.flags & kTypeDelete) != 0;   // crc32 0 and, by default, hash 0 (see the small kernel)
+    const uint32_t crc = del ? 0u : crc::extend_wave(0u, (uint64_t)klen + L.crc_bytes, msg, s_t);
 
     if (lane == 0) {
       const uint64_t h = hash_type == 1 ? xxh64(key, klen) : murmur3_64(key, klen);
+      const uint64_t hh = del && !delete_hashed ? 0u : h;
       hashed[v] = h;
       crc_out[v] = crc;
       uint8_t* q = hdr + 1;
@@ -449,7 +482,7 @@ __global__ __launch_bounds__(kEntryBlock) void put_entry_kernel(
       q = put_varint(q, V);
       for (int i = 0; i < 8; i++) *q++ = (uint8_t)(L.svc_hdr >> (8 * i));
       q = put_varint(q, L.pad_hdr);
-      for (int i = 0; i < 8; i++) *q++ = (uint8_t)(h >> (8 * i));
+      for (int i = 0; i < 8; i++) *q++ = (uint8_t)(hh >> (8 * i));
       uint32_t c8 = 0xffu;                        // crc8(0, header + 1, hl - 1)
       for (uint32_t i = 1; i < hl; i++) c8 = s_c8[(c8 ^ hdr[i]) & 0xffu];
       hdr[0] = (uint8_t)(c8 ^ 0xffu);
@@ -466,7 +499,7 @@ __global__ void zero_u64_kernel(uint64_t* p) { *p = 0; }
 
 }  // namespace
 
-// Device scratch the batch needs (see kdb_put_entries_batch).
+// Device scratch the batch needs (see kdb_put_ops_batch).
 uint64_t put_scratch_bytes(uint32_t n, uint32_t nparts, uint64_t raw_bytes) {
   const uint64_t frames = raw_bytes + raw_bytes / 255u + (uint64_t)nparts * 40u + 64u;
   const uint64_t parts = (uint64_t)nparts * (8 + 4 + 8 + 4 + 4 + 8 + 4 + 4);
@@ -475,7 +508,7 @@ uint64_t put_scratch_bytes(uint32_t n, uint32_t nparts, uint64_t raw_bytes) {
   return frames + parts + vals + 13u * 256u;
 }
 
-hipError_t launch_put_entries(hipStream_t st, const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len,
+hipError_t launch_put_entries(hipStream_t st, const uint8_t* op, uint32_t flags, const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len,
                               const uint8_t* values, const uint64_t* value_off, const uint64_t* value_len,
                               const uint32_t* part_first, const uint32_t* chunk_len, uint32_t nparts,
                               uint32_t max_chunk, uint32_t n, uint32_t hash_type, uint8_t* scratch,
@@ -520,7 +553,7 @@ hipError_t launch_put_entries(hipStream_t st, const uint8_t* keys, const uint64_
     const hipError_t e = hipMemsetAsync(big, 0, 4, st);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(put_policy_kernel, dim3(tg), dim3(tb), 0, st, key_len, value_len, part_first, chunk_len,
+  hipLaunchKernelGGL(put_policy_kernel, dim3(tg), dim3(tb), 0, st, op, key_len, value_len, part_first, chunk_len,
                      frame_len, fstatus, n, occ, plen, mode, lay, entry_len, big);
   {
     const hipError_t e = launch_exclusive_scan(st, entry_len, n, entry_off, total);
@@ -529,11 +562,12 @@ hipError_t launch_put_entries(hipStream_t st, const uint8_t* keys, const uint64_
   const uint32_t eg = (n + 3) / 4 < 16384u ? (n + 3) / 4 : 16384u;
   PartSrc ps{values, frames, part_src, frame_off, mode};
   const uint32_t sg = (n + 255) / 256 < 4096u ? (n + 255) / 256 : 4096u;
+  const uint32_t dh = (flags & KDB_OPS_DELETE_HASHED) ? 1u : 0u;
   hipLaunchKernelGGL(put_entry_small_kernel, dim3(sg), dim3(256), 0, st, keys, key_off, key_len, value_len,
-                     part_first, ps, occ, plen, lay, n, hash_type, entries, entry_off, hashed, crc, kind, status);
+                     part_first, ps, occ, plen, lay, n, hash_type, dh, entries, entry_off, hashed, crc, kind, status);
   hipLaunchKernelGGL(put_entry_kernel, dim3(eg), dim3(kEntryBlock), 0, st, keys, key_off, key_len, value_len,
-                     part_first, ps, occ, plen, lay, n, hash_type, entries, entry_off, entry_len, hashed, crc, kind,
-                     status, big);
+                     part_first, ps, occ, plen, lay, n, hash_type, dh, entries, entry_off, entry_len, hashed, crc,
+                     kind, status, big);
   return hipGetLastError();
 }
 
@@ -546,6 +580,28 @@ extern "C" uint64_t kdb_put_scratch_bytes(uint32_t n, uint32_t nparts, uint64_t 
   return put_scratch_bytes(n, nparts, raw_bytes);
 }
 
+extern "C" int kdb_put_ops_batch(void* stream, const uint8_t* op, uint32_t flags, const uint8_t* keys,
+                                 const uint64_t* key_off, const uint32_t* key_len, const uint8_t* values,
+                                 const uint64_t* value_off, const uint64_t* value_len, const uint32_t* part_first,
+                                 const uint32_t* chunk_len, uint32_t nparts, uint32_t max_chunk, uint32_t n,
+                                 uint32_t hash_type, uint8_t* scratch, uint64_t scratch_bytes, uint64_t raw_bytes,
+                                 uint8_t* entries, uint64_t* entry_off, uint32_t* entry_len, uint64_t* total,
+                                 uint64_t* hashed, uint32_t* crc, uint32_t* kind, int32_t* status) {
+  if (!total || (n && (!keys || !key_off || !key_len || !value_off || !value_len || !part_first || !entries ||
+                       !entry_off || !entry_len || !hashed || !crc || !kind || !status || !scratch)) ||
+      (nparts && (!values || !chunk_len)) || hash_type > 1 || max_chunk > kMaxInput ||
+      (flags & ~KDB_OPS_DELETE_HASHED))
+    return KDB_LZ4_EINVAL;
+  if (scratch_bytes < put_scratch_bytes(n, nparts, raw_bytes)) return KDB_LZ4_EINVAL;
+  const hipError_t e = launch_put_entries((hipStream_t)stream, op, flags, keys, key_off, key_len, values, value_off,
+                                          value_len, part_first, chunk_len, nparts, max_chunk, n, hash_type, scratch,
+                                          scratch_bytes, raw_bytes, entries, entry_off, entry_len, total, hashed, crc,
+                                          kind, status);
+  if (e == hipSuccess) return KDB_LZ4_OK;
+  return (e == hipErrorNoDevice || e == hipErrorInvalidDevice) ? KDB_LZ4_ENODEV : KDB_LZ4_EHIP;
+}
+
+// every op a put, the reference's bytes
 extern "C" int kdb_put_entries_batch(void* stream, const uint8_t* keys, const uint64_t* key_off,
                                      const uint32_t* key_len, const uint8_t* values, const uint64_t* value_off,
                                      const uint64_t* value_len, const uint32_t* part_first,
@@ -554,15 +610,7 @@ extern "C" int kdb_put_entries_batch(void* stream, const uint8_t* keys, const ui
                                      uint64_t raw_bytes, uint8_t* entries, uint64_t* entry_off,
                                      uint32_t* entry_len, uint64_t* total, uint64_t* hashed, uint32_t* crc,
                                      uint32_t* kind, int32_t* status) {
-  if (!total || (n && (!keys || !key_off || !key_len || !value_off || !value_len || !part_first || !entries ||
-                       !entry_off || !entry_len || !hashed || !crc || !kind || !status || !scratch)) ||
-      (nparts && (!values || !chunk_len)) || hash_type > 1 || max_chunk > kMaxInput)
-    return KDB_LZ4_EINVAL;
-  if (scratch_bytes < put_scratch_bytes(n, nparts, raw_bytes)) return KDB_LZ4_EINVAL;
-  const hipError_t e = launch_put_entries((hipStream_t)stream, keys, key_off, key_len, values, value_off, value_len,
-                                          part_first, chunk_len, nparts, max_chunk, n, hash_type, scratch,
-                                          scratch_bytes, raw_bytes, entries, entry_off, entry_len, total, hashed, crc,
-                                          kind, status);
-  if (e == hipSuccess) return KDB_LZ4_OK;
-  return (e == hipErrorNoDevice || e == hipErrorInvalidDevice) ? KDB_LZ4_ENODEV : KDB_LZ4_EHIP;
+  return kdb_put_ops_batch(stream, nullptr, 0u, keys, key_off, key_len, values, value_off, value_len, part_first,
+                           chunk_len, nparts, max_chunk, n, hash_type, scratch, scratch_bytes, raw_bytes, entries,
+                           entry_off, entry_len, total, hashed, crc, kind, status);
 }

@@ -53,6 +53,11 @@ class Entry:
     header_size: int
 
     @property
+    def is_delete(self) -> bool:
+        """A delete entry (EntryHeader::IsTypeDelete): header and key, no value."""
+        return bool(self.flags & 0x1)
+
+    @property
     def stored_len(self) -> int:
         """Bytes of the value region that hold data (EntryHeader::size_value_used)."""
         return self.size_value_compressed if self.size_value_compressed else self.size_value

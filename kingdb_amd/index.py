@@ -23,7 +23,8 @@ set of closed HSTable files and the batched lookup in front of the decoder.
                           the same for an uploaded index: new files go into
                           the N spare bytes behind the first ones
 
-status: 0 OK, NOTFOUND, DELETED (Database::Get reports NotFound), MULTIPART
+status: 0 OK, NOTFOUND, DELETED (the newest entry is a delete: Database::Get
+returns a Status of code kDeleteOrder, or NotFound from the write buffer), MULTIPART
 (MultipartRequired), or the decoder's -1 / -2 (see get.py).  Databases opened
 with compression enabled only.  A file without a usable footer (status -1 in
 `.file_status`: the newest file after a crash) is left out unless

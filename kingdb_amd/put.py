@@ -16,6 +16,11 @@ framing on the host (csrc/hstable.cc).
 A put is (key, value) or (key, value, chunks): `chunks` lists the sizes of
 the PutPart calls the value arrives in (default: one call, i.e. Database::Put
 of a value <= maximum_part_size; use split_parts() for Put's own splitting).
+An item (key, DELETE) is Database::Delete of the key (include/kdb_ops.h): a
+delete entry, header and key, in the place a put's entry would take.  It has
+no value, so giving it chunks is a ValueError.  By default its bytes are the
+reference's, header hash field 0; delete_hashed=True writes the key's hash
+there, which keeps the delete reachable when its file has to be recovered.
 Nothing here computes on the CPU except that host-side framing.
 """
 from __future__ import annotations
@@ -30,6 +35,22 @@ from .lz4 import DeviceBuffer, Stream
 
 SELF_CONTAINED, MULTIPART, MULTIPART_UNFINISHED = 0, 1, 2
 MAX_PART_SIZE = 1 << 20          # storage__maximum_part_size default (util/options.h:170-172)
+OP_PUT, OP_DELETE = 0, 1         # KDB_OP_PUT, KDB_OP_DELETE
+OPS_DELETE_HASHED = 1            # KDB_OPS_DELETE_HASHED
+
+
+class _Delete:
+    """The value of a delete item: (key, DELETE)."""
+
+    def __repr__(self) -> str:
+        return "DELETE"
+
+
+DELETE = _Delete()
+
+
+def is_delete(item) -> bool:
+    return item[1] is DELETE
 
 
 def lib():
@@ -77,13 +98,14 @@ class PutBatch:
         # per value: key_off u64, key_len u32, value_off u64, value_len u64, part_first u32 (n+1)
         self.vmeta = DeviceBuffer(n * 32 + 8)
         self.chunks = DeviceBuffer(nparts * 4 + 4)
+        self.ops = DeviceBuffer(n + 8)           # one KDB_OP_* byte per item (read only where a batch has deletes)
         self.entries_cap = raw + n * 64 + key_bytes + (raw // 65536 + 1) * 8 * 2 + n * 8 + 64
         self.entries = DeviceBuffer(self.entries_cap)
         # outputs: entry_off u64, entry_len u32, hashed u64, crc u32, kind u32, status i32, total u64
         self.out = DeviceBuffer(n * 32 + 64)
 
     def free(self) -> None:
-        for b in (self.scratch, self.keys, self.values, self.vmeta, self.chunks, self.entries, self.out):
+        for b in (self.scratch, self.keys, self.values, self.vmeta, self.chunks, self.ops, self.entries, self.out):
             b.free()
 
     def _optr(self, n: int):
@@ -91,23 +113,36 @@ class PutBatch:
         return dict(entry_off=o, entry_len=o + 8 * n, hashed=o + 12 * n, crc=o + 20 * n, kind=o + 24 * n,
                     status=o + 28 * n, total=o + 32 * n)
 
-    def run_device(self, stream, n: int, nparts: int, max_chunk: int, raw: int, hash_type: int) -> None:
-        """Launches kdb_put_entries_batch on what is already resident."""
+    def run_device(self, stream, n: int, nparts: int, max_chunk: int, raw: int, hash_type: int,
+                   delete_hashed: bool = False, ops: bool = False) -> None:
+        """Launches kdb_put_ops_batch on what is already resident.  ops: the
+        batch has deletes and `self.ops` holds its n op bytes (otherwise every
+        item is a put and the buffer is not read)."""
         if n > self.n or nparts > self.nparts or raw > self.raw:
             raise ValueError("batch larger than the buffers")
         v, c = self.vmeta.ptr, self.n     # metadata laid out for the capacity (a short batch uses a prefix)
         o = self._optr(n)
-        _lib.check(lib().kdb_put_entries_batch(
-            stream.ptr if stream else None, self.keys.ptr, v, v + 8 * c, self.values.ptr, v + 12 * c, v + 20 * c,
+        _lib.check(lib().kdb_put_ops_batch(
+            stream.ptr if stream else None, self.ops.ptr if ops else None, OPS_DELETE_HASHED if delete_hashed else 0,
+            self.keys.ptr, v, v + 8 * c, self.values.ptr, v + 12 * c, v + 20 * c,
             v + 28 * c, self.chunks.ptr, nparts, max_chunk, n, hash_type, self.scratch.ptr, self.scratch_bytes, raw,
             self.entries.ptr, o["entry_off"], o["entry_len"], o["total"], o["hashed"], o["crc"], o["kind"],
-            o["status"]), "kdb_put_entries_batch")
+            o["status"]), "kdb_put_ops_batch")
 
 
 def _layout(puts):
+    """The input arrays of kdb_put_ops_batch; the last is the op bytes, or
+    None where no item is a delete."""
     keys = [p[0] for p in puts]
-    vals = [p[1] for p in puts]
-    chunks = [list(p[2]) if len(p) > 2 and p[2] is not None else [len(p[1])] for p in puts]
+    dels = [is_delete(p) for p in puts]
+    for p, d in zip(puts, dels):
+        if d and len(p) > 2 and p[2] is not None:
+            raise ValueError("a delete has no value: it takes no chunks")
+    # a delete: value_len 0 and no chunk
+    vals = [b"" if d else p[1] for p, d in zip(puts, dels)]
+    chunks = [[] if d else list(p[2]) if len(p) > 2 and p[2] is not None else [len(p[1])]
+              for p, d in zip(puts, dels)]
+    ops = np.array(dels, np.uint8) if any(dels) else None
     for v, ch in zip(vals, chunks):
         if sum(ch) != len(v):
             raise ValueError("chunk sizes must add up to the value size")
@@ -125,12 +160,13 @@ def _layout(puts):
     clen = np.array([c for ch in chunks for c in ch], np.uint32)
     kbuf = np.frombuffer(b"".join(keys), np.uint8) if n else np.zeros(0, np.uint8)
     vbuf = np.frombuffer(b"".join(vals), np.uint8) if n else np.zeros(0, np.uint8)
-    return kbuf, vbuf, koff, klen, voff, vlen, pf, clen
+    return kbuf, vbuf, koff, klen, voff, vlen, pf, clen, ops
 
 
-def put_entries(puts, hash_type: int = 1, stream: Stream | None = None) -> PutBatchResult:
-    """One GPU batch: the HSTable entry bytes of every put (see kdb_put.h)."""
-    kbuf, vbuf, koff, klen, voff, vlen, pf, clen = _layout(puts)
+def put_entries(puts, hash_type: int = 1, stream: Stream | None = None, delete_hashed: bool = False
+                ) -> PutBatchResult:
+    """One GPU batch: the HSTable entry bytes of every put and delete (see kdb_put.h, kdb_ops.h)."""
+    kbuf, vbuf, koff, klen, voff, vlen, pf, clen, ops = _layout(puts)
     n = len(puts)
     nparts = len(clen)
     raw = int(vlen.sum()) if n else 0
@@ -146,7 +182,10 @@ def put_entries(puts, hash_type: int = 1, stream: Stream | None = None) -> PutBa
         b.vmeta.upload(meta, stream=st)
         if nparts:
             b.chunks.upload(clen, stream=st)
-        b.run_device(stream, n, nparts, int(clen.max()) if nparts else 0, raw, hash_type)
+        if ops is not None:
+            b.ops.upload(ops, stream=st)
+        b.run_device(stream, n, nparts, int(clen.max()) if nparts else 0, raw, hash_type, delete_hashed,
+                     ops is not None)
         o = b._optr(n)
         # the copies back ride the caller's stream (see get_values)
         out = b.out.download(32 * n + 8, 0, stream=st)
@@ -240,22 +279,23 @@ def db_options(hstable_size: int = 32 << 20, hash_type: int = 1) -> bytes:
     return out.tobytes()
 
 
-def write_hstables(puts, hstable_size: int = 32 << 20, hash_type: int = 1, batch: int | None = None
-                   ) -> dict[str, bytes]:
+def write_hstables(puts, hstable_size: int = 32 << 20, hash_type: int = 1, batch: int | None = None,
+                   delete_hashed: bool = False) -> dict[str, bytes]:
     """The HSTable files KingDB writes for `puts` (one writer thread), with
     the puts handed to the GPU `batch` at a time (one write-buffer flush each)."""
     w = HSTableWriter(hstable_size, hash_type)
     step = batch or max(len(puts), 1)
     for i in range(0, len(puts), step):
-        w.append(put_entries(puts[i:i + step], hash_type))
+        w.append(put_entries(puts[i:i + step], hash_type, delete_hashed=delete_hashed))
     w.close()
     return w.files()
 
 
-def put_entries_device(puts, hash_type: int = 1, stream: Stream | None = None) -> tuple[PutBatch, int]:
+def put_entries_device(puts, hash_type: int = 1, stream: Stream | None = None, delete_hashed: bool = False
+                       ) -> tuple[PutBatch, int]:
     """put_entries() that leaves its outputs where they are: (the PutBatch
     holding them in device memory, n).  The caller frees the batch."""
-    kbuf, vbuf, koff, klen, voff, vlen, pf, clen = _layout(puts)
+    kbuf, vbuf, koff, klen, voff, vlen, pf, clen, ops = _layout(puts)
     n = len(puts)
     nparts = len(clen)
     raw = int(vlen.sum()) if n else 0
@@ -275,16 +315,20 @@ def put_entries_device(puts, hash_type: int = 1, stream: Stream | None = None) -
         b.vmeta.upload(meta, stream=st)
         if nparts:
             b.chunks.upload(clen, stream=st)
-        b.run_device(stream, n, nparts, int(clen.max()) if nparts else 0, raw, hash_type)
+        if ops is not None:
+            b.ops.upload(ops, stream=st)
+        b.run_device(stream, n, nparts, int(clen.max()) if nparts else 0, raw, hash_type, delete_hashed,
+                     ops is not None)
     except Exception:
         b.free()
         raise
     return b, n
 
 
-def entries_bound(puts) -> int:
-    """An upper bound on the entry bytes `puts` make (PutBatch's own sizing)."""
-    raw = sum(len(p[1]) for p in puts)
+def entries_bound(puts, delete_hashed: bool = False) -> int:
+    """An upper bound on the entry bytes `puts` make (PutBatch's own sizing);
+    a delete's entry has the same size with either header hash."""
+    raw = sum(0 if is_delete(p) else len(p[1]) for p in puts)
     return raw + sum(len(p[0]) for p in puts) + len(puts) * 72 + (raw // 65536 + len(puts) + 1) * 16 + 64
 
 
@@ -364,8 +408,8 @@ class DeviceHSTableWriter:
             pass
 
 
-def write_hstables_device(puts, hstable_size: int = 32 << 20, hash_type: int = 1, batch: int | None = None
-                          ) -> dict[str, bytes]:
+def write_hstables_device(puts, hstable_size: int = 32 << 20, hash_type: int = 1, batch: int | None = None,
+                          delete_hashed: bool = False) -> dict[str, bytes]:
     """write_hstables() with both stages on the device: the entries never
     leave it, only the finished files come back."""
     step = batch or max(len(puts), 1)
@@ -374,7 +418,7 @@ def write_hstables_device(puts, hstable_size: int = 32 << 20, hash_type: int = 1
                             DeviceHSTableWriter.arena_bytes(hstable_size, bound, len(puts)))
     try:
         for i in range(0, len(puts), step):
-            b, n = put_entries_device(puts[i:i + step], hash_type)
+            b, n = put_entries_device(puts[i:i + step], hash_type, delete_hashed=delete_hashed)
             try:
                 w.append_batch(b, n)
                 _lib.check(lib().kdb_lz4_stream_sync(None), "sync")     # the batch's buffers are read by queued work

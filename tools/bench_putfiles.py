@@ -2,9 +2,12 @@
 """HSTable framing measured: the host writer against the device writer.
 
     python tools/bench_putfiles.py [--puts 1048576] [--steps 20] [--warmup 3]
-                                   [--compact-steps 3] [--no-compact]
+                                   [--compact-steps 3] [--no-compact] [--deletes PCT]
 
 Set: `--puts` x (16 B key "%016d", 100 B G1 value), hstable_size 32 MiB.
+`--deletes PCT` (default 0: the set and the output above, unchanged) replaces
+that share of the puts by deletes of earlier keys (put.DELETE): item j with
+j % 100 < PCT deletes key j // 2.
 kdb_put_entries_batch runs once, before any timing: every leg frames the same
 entries, resident in device memory.  The legs run interleaved, one after the
 other in every step, in one process on one device; each is a synchronous
@@ -55,6 +58,7 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--compact-steps", type=int, default=3)
     ap.add_argument("--no-compact", action="store_true")
+    ap.add_argument("--deletes", type=int, default=0, metavar="PCT")
     a = ap.parse_args()
     if K.device_count() < 1:
         raise SystemExit("bench_putfiles: no GPU visible to libkdb_lz4.so")
@@ -63,7 +67,15 @@ def main() -> None:
     n = a.puts
     orc = oracle.Oracle()
     pool = oracle.g1_pool(orc, 4 << 20)
+    if not 0 <= a.deletes <= 100:
+        raise SystemExit("bench_putfiles: --deletes takes a percentage")
     puts = [(b"%016d" % j, pool[(100 * j) % (len(pool) - 100):][:100].tobytes()) for j in range(n)]
+    ndel = 0
+    if a.deletes:
+        for j in range(1, n):
+            if j % 100 < a.deletes:
+                puts[j] = (b"%016d" % (j // 2), put.DELETE)
+                ndel += 1
     stream = Stream()
     st = stream.ptr
     b, _ = put.put_entries_device(puts, 1, stream)          # once: the framing is measured alone
@@ -168,6 +180,8 @@ def main() -> None:
         print(f"step {step}", file=sys.stderr, flush=True)
     res = {"bench": "putfiles", "puts": n, "hstable_size": HS, "files": nfiles, "file_bytes": file_bytes,
            "entry_bytes": total, "steps": a.steps, "warmup": a.warmup}
+    if a.deletes:
+        res.update(deletes_pct=a.deletes, deletes=ndel)
     for name in legs:
         res[name] = stats(ms[name])
     lib.kdb_index_destroy(ixh.value)
