@@ -97,6 +97,15 @@ SIGNATURES = {
     # include/kdb_index_add.h (newly closed files added to a loaded index)
     "kdb_index_add_files": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _c.POINTER(_u64)]),
     "kdb_index_add_stats": (_i, [_vp, _c.POINTER(_u32), _c.POINTER(_u64), _c.POINTER(_u64)]),
+    # include/kdb_snapshot.h (a loaded index read as of a point); the batch calls take their kdb_index_* twins' lists
+    "kdb_snapshot_create": (_i, [_vp, _c.POINTER(_vp)]),
+    "kdb_snapshot_release": (_i, [_vp]),
+    "kdb_snapshot_entry_count": (_i, [_vp, _c.POINTER(_u64)]),
+    "kdb_snapshot_file_count": (_i, [_vp, _c.POINTER(_u32)]),
+    "kdb_snapshot_get_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _i, _u64, _vp, _u64] + [_vp] * 10),
+    "kdb_snapshot_scan_prepare": (_i, [_vp, _vp, _i, _c.POINTER(_u64), _c.POINTER(_u64), _c.POINTER(_u32)]),
+    "kdb_snapshot_scan_sort_steps": (_i, [_vp, _c.POINTER(_u32)]),
+    "kdb_snapshot_scan_batch": (_i, [_vp, _vp, _u64, _u32, _u64, _vp, _u64, _vp, _u64, _vp, _vp] + [_vp] * 10),
     "kdb_hstable_db_options": (_i, [_u64, _u32, _vp]),
     "kdb_hstable_writer_create": (_i, [_u64, _u32, _c.POINTER(_vp)]),
     "kdb_hstable_writer_create2": (_i, [_u64, _u32, _u32, _c.POINTER(_vp)]),

@@ -37,6 +37,13 @@
 //                        (hstable_decode.h), key compare and crc32c(key) on the lanes
 //   scan                 64-byte-aligned output slots
 //   index_summary_kernel what the host needs to size the decode
+// Snapshot (include/kdb_snapshot.h; Database::NewSnapshot, interface/database.cc:301-327,
+// interface/snapshot.h): a row limit R, the handle's row count when it was
+// taken.  Rows keep their sequence numbers through every add, so the lookup
+// and the liveness pass restricted to rows of sequence number < R, over the
+// handle's current buckets, answer as a handle loaded over the files held
+// then: index_get_kernel<true>, index_live_kernel<true>, and the scan's other
+// kernels over the snapshot's own list
 // Scan (include/kdb_scan.h; Database::NewIterator, interface/iterator.h:112-214):
 //   index_live_kernel    wave per row: the row is live iff the lookup of its
 //                        own stored key would select it (prepare, synchronous)
@@ -290,6 +297,12 @@ __device__ __forceinline__ uint64_t wave_sum64(uint64_t x) {
 
 // Wave per key.  Everything but the bucket scan, the key compare and the
 // key's CRC is the same on every lane (same addresses: broadcast loads).
+// kLimited (a snapshot's lookup): ix.nrows is the snapshot's row limit R, not
+// the handle's row count, and only slots with seq < R are candidates.  The
+// limit rides in a field the kernel reads already, and the `false` form is the
+// kernel kdb_index_get_batch has always launched, instruction for instruction
+// (same resource figures).
+template <bool kLimited>
 __global__ __launch_bounds__(kGetBlock) void index_get_kernel(
     IndexView ix, const uint8_t* __restrict__ keys, const uint64_t* __restrict__ key_off,
     const uint32_t* __restrict__ key_len, uint32_t n, int verify_header, uint64_t multipart_required,
@@ -324,7 +337,9 @@ __global__ __launch_bounds__(kGetBlock) void index_get_kernel(
     if (ix.nrows) {
       const uint64_t b = h & ix.mask;
       const uint64_t s0 = ix.start[b], s1 = ix.start[b + 1u];
-      uint64_t bound = ~0ull;               // candidates taken so far have (seq + 1) << 32 | slot >= bound
+      // candidates taken so far have (seq + 1) << 32 | slot >= bound; slot < 2^32,
+      // so (R + 1) << 32 admits exactly the slots with seq < R
+      uint64_t bound = kLimited ? ((uint64_t)ix.nrows + 1u) << 32 : ~0ull;
       for (;;) {
         uint64_t best = 0;
         for (uint64_t i = s0 + lane; i < s1; i += 64u) {
@@ -442,19 +457,22 @@ __device__ __forceinline__ bool stage_entry_header(const uint8_t* file, uint64_t
 // packed rank (seq + 1) << 32 | position lies above `floor`, newest first, the
 // first whose header decodes, is valid (GetWithIndex:446 skips the others) and
 // whose stored key equals key[0 .. klen).  floor 0 takes every row;
-// (r + 1) << 32 | 0xFFFFFFFF only the rows newer than row r.
+// (r + 1) << 32 | 0xFFFFFFFF only the rows newer than row r.  `top` is the
+// walk's first bound: ~0 takes every row above the floor, (R + 1) << 32 only
+// the rows of sequence number < R (a snapshot: rows >= R do not exist for it).
 // A second copy of the walk, on purpose: with index_get_kernel calling this
 // function instead of its own loop, `locate` measured 3.55-3.57 ms against the
 // 3.52-3.53 ms of the unchanged kernel, interleaved on one device (126 VGPRs
 // against 125, another spill pattern), which is outside that kernel's own
 // run-to-run spread.  So the lookup keeps its text.
 __device__ __forceinline__ bool find_candidate(const IndexView& ix, uint64_t h, const uint8_t* key, uint32_t klen,
-                                               uint64_t floor, int verify_header, uint8_t* s_hdr, uint32_t lane,
-                                               Slot* c_out, hs::EntryHeader* hd_out, uint64_t* fo_out) {
+                                               uint64_t floor, uint64_t top, int verify_header, uint8_t* s_hdr,
+                                               uint32_t lane, Slot* c_out, hs::EntryHeader* hd_out,
+                                               uint64_t* fo_out) {
   if (ix.nrows == 0) return false;
   const uint64_t b = h & ix.mask;
   const uint64_t s0 = ix.start[b], s1 = ix.start[b + 1u];
-  uint64_t bound = ~0ull;               // candidates taken so far have (seq + 1) << 32 | slot >= bound
+  uint64_t bound = top;                 // candidates taken so far have (seq + 1) << 32 | slot >= bound
   for (;;) {
     uint64_t best = floor;
     for (uint64_t i = s0 + lane; i < s1; i += 64u) {
@@ -506,6 +524,12 @@ struct RowView {
 // stored key is the row's hash (else Get cannot reach the row); and no newer
 // equal-hash row holds a valid entry with the same key.  klen[r] = the key's
 // length for a live row, 0 for a dead one (a valid entry's key is not empty).
+// kLimited (a snapshot's prepare): ix.nrows is the snapshot's row limit R; the
+// pass runs over rows r < R and the walk over newer equal-hash rows examines
+// the rows in (r, R) only, so a row whose key is overwritten or deleted only
+// by a row >= R is live.  The `false` form passes the constant ~0 and is the
+// kernel the handle's own prepare has always run.
+template <bool kLimited>
 __global__ __launch_bounds__(kGetBlock) void index_live_kernel(IndexView ix, RowView rows, int verify_header,
                                                                uint32_t* __restrict__ flag,
                                                                uint32_t* __restrict__ klen_out,
@@ -541,7 +565,8 @@ __global__ __launch_bounds__(kGetBlock) void index_live_kernel(IndexView ix, Row
       hs::EntryHeader ch;
       uint64_t cfo;
       // no newer equal-hash row (the common case): live without a second header read
-      if (hk == h && !find_candidate(ix, h, key, klen, ((uint64_t)r + 1u) << 32 | 0xFFFFFFFFull, verify_header,
+      if (hk == h && !find_candidate(ix, h, key, klen, ((uint64_t)r + 1u) << 32 | 0xFFFFFFFFull,
+                                     kLimited ? ((uint64_t)ix.nrows + 1u) << 32 : ~0ull, verify_header,
                                      s_hdr[wib], lane, &c, &ch, &cfo))
         live_len = klen;
     }
@@ -671,6 +696,19 @@ __global__ __launch_bounds__(kGetBlock) void index_scan_emit_kernel(
 
 using namespace kdb_lz4;
 
+// A prepared scan (kdb_index_scan_prepare, kdb_snapshot_scan_prepare): the
+// live list, rank << 32 | offset in iterator order, and the exclusive sum of
+// the live keys' lengths (live + 1 entries, on the device for the emit and on
+// the host for the window checks).  The handle has one and every snapshot its own.
+struct ScanState {
+  bool ready = false;
+  uint64_t live = 0;
+  uint32_t sort_steps = 0;
+  uint64_t* d_live = nullptr;
+  uint64_t* d_key_prefix = nullptr;
+  std::vector<uint64_t> key_prefix;
+};
+
 struct kdb_index {
   uint32_t hash_type = 1;
   const uint8_t* d_files = nullptr;      // the caller's
@@ -698,15 +736,20 @@ struct kdb_index {
   // kdb_index_add_stats
   bool add_done = false;
   uint64_t add_rows_parsed = 0;
-  // the scan's live list (kdb_index_scan_prepare): rank << 32 | offset in
-  // iterator order, and the exclusive sum of the live keys' lengths (live + 1
-  // entries, on the device for the emit and on the host for the window checks)
-  bool scan_ready = false;
-  uint64_t live = 0;
-  uint32_t sort_steps = 0;
-  uint64_t* d_live = nullptr;
-  uint64_t* d_key_prefix = nullptr;
-  std::vector<uint64_t> key_prefix;
+  ScanState scan;                        // kdb_index_scan_prepare: dropped by every add
+  // open kdb_snapshots: while there are any, the rows keep their sequence
+  // numbers (no load) and the handle stays (no destroy)
+  uint32_t snapshots = 0;
+};
+
+// The handle as of kdb_snapshot_create: its first `nrows` rows, `nfiles` file
+// slots and `nloaded` ranks.  Everything else is read from the handle as it is
+// when a call comes: the rows, slots and ranks below these counts do not move.
+struct kdb_snapshot {
+  kdb_index* ix = nullptr;
+  uint64_t nrows = 0;
+  uint32_t nfiles = 0, nloaded = 0;
+  ScanState scan;
 };
 
 namespace {
@@ -717,17 +760,17 @@ void dfree(T*& p) {
   p = nullptr;
 }
 
-void scan_release(kdb_index* ix) {
-  dfree(ix->d_live);
-  dfree(ix->d_key_prefix);
-  ix->key_prefix.clear();
-  ix->scan_ready = false;
-  ix->live = 0;
-  ix->sort_steps = 0;
+void scan_release(ScanState* sc) {
+  dfree(sc->d_live);
+  dfree(sc->d_key_prefix);
+  sc->key_prefix.clear();
+  sc->ready = false;
+  sc->live = 0;
+  sc->sort_steps = 0;
 }
 
 void index_release(kdb_index* ix) {
-  scan_release(ix);
+  scan_release(&ix->scan);
   dfree(ix->d_file_rank);
   dfree(ix->d_rank_file);
   dfree(ix->d_file_off);
@@ -998,7 +1041,7 @@ hipError_t index_add(kdb_index* ix, hipStream_t st, const uint64_t* file_off, co
   ix->nfiles = nf;
   ix->nrows = nrows;
   ix->nbuckets = B;
-  scan_release(ix);
+  scan_release(&ix->scan);               // the handle's own; a snapshot's list stands on rows that did not move
   ix->add_done = true;
   ix->add_rows_parsed = rows_parsed;
   *rows_added = rows_new;
@@ -1018,7 +1061,7 @@ extern "C" int kdb_index_create(uint32_t hash_type, kdb_index** ix) {
 }
 
 extern "C" int kdb_index_destroy(kdb_index* ix) {
-  if (!ix) return KDB_PUT_EINVAL;
+  if (!ix || ix->snapshots) return KDB_PUT_EINVAL;
   index_release(ix);
   delete ix;
   return KDB_PUT_OK;
@@ -1027,7 +1070,7 @@ extern "C" int kdb_index_destroy(kdb_index* ix) {
 extern "C" int kdb_index_load_files(kdb_index* ix, void* stream, const uint8_t* d_files, const uint64_t* file_off,
                                     const uint64_t* file_size, const uint32_t* fileid, uint32_t nfiles,
                                     int32_t* file_status_out, uint64_t* entries_out) {
-  if (!ix || (nfiles && (!d_files || !file_off || !file_size || !fileid || !file_status_out)))
+  if (!ix || ix->snapshots || (nfiles && (!d_files || !file_off || !file_size || !fileid || !file_status_out)))
     return KDB_PUT_EINVAL;
   for (uint32_t f = 0; f < nfiles; f++)
     if (file_size[f] > hs::kMaxFileSize) return KDB_PUT_EINVAL;
@@ -1103,12 +1146,15 @@ extern "C" int kdb_index_pairs(const kdb_index* ix, uint64_t* hash_out, uint64_t
 
 extern "C" uint64_t kdb_index_get_scratch_bytes(uint32_t n) { return (uint64_t)n * 4u + 256u; }
 
-extern "C" int kdb_index_get_batch(const kdb_index* ix, void* stream, const uint8_t* keys, const uint64_t* key_off,
-                                   const uint32_t* key_len, uint32_t n, int verify_header,
-                                   uint64_t multipart_required, uint8_t* scratch, uint64_t scratch_bytes,
-                                   uint64_t* stored_off, uint64_t* avail, uint64_t* svc, uint64_t* size,
-                                   uint32_t* checksum, uint32_t* checksum_initial, uint64_t* out_off,
-                                   uint64_t* location, int32_t* status, uint64_t* summary) {
+namespace {
+
+// kdb_index_get_batch (snap = nullptr) and kdb_snapshot_get_batch: the same
+// checks, scan and summary around index_get_kernel<false> and <true>.
+int lookup_batch(const kdb_index* ix, const kdb_snapshot* snap, void* stream, const uint8_t* keys,
+                 const uint64_t* key_off, const uint32_t* key_len, uint32_t n, int verify_header,
+                 uint64_t multipart_required, uint8_t* scratch, uint64_t scratch_bytes, uint64_t* stored_off,
+                 uint64_t* avail, uint64_t* svc, uint64_t* size, uint32_t* checksum, uint32_t* checksum_initial,
+                 uint64_t* out_off, uint64_t* location, int32_t* status, uint64_t* summary) {
   if (multipart_required == 0) multipart_required = 1048576u;    // internal__size_multipart_required
   if (!ix || !summary || verify_header < 0 || verify_header > 1 || multipart_required > (1ull << 31) ||
       scratch_bytes < kdb_index_get_scratch_bytes(n) ||
@@ -1120,13 +1166,20 @@ extern "C" int kdb_index_get_batch(const kdb_index* ix, void* stream, const uint
   if (e != hipSuccess) return hip_code(e);
   if (n == 0) return KDB_PUT_OK;
   uint32_t* slot_len = reinterpret_cast<uint32_t*>(scratch);
+  // a snapshot: the handle's arrays as they are now, the row count its own limit
   const IndexView view{ix->d_files,  ix->d_file_off, ix->d_file_size,        ix->d_fileid, ix->d_start,
-                       ix->d_slots,  ix->nbuckets ? ix->nbuckets - 1u : 0u, (uint32_t)ix->nrows, ix->hash_type};
+                       ix->d_slots,  ix->nbuckets ? ix->nbuckets - 1u : 0u, (uint32_t)(snap ? snap->nrows : ix->nrows),
+                       ix->hash_type};
   const uint32_t waves = kGetBlock / 64;
   const uint32_t g = std::min<uint32_t>((n + waves - 1u) / waves, 16384u);
-  hipLaunchKernelGGL(index_get_kernel, dim3(g), dim3(kGetBlock), 0, st, view, keys, key_off, key_len, n,
-                     verify_header, multipart_required, stored_off, avail, svc, size, checksum, checksum_initial,
-                     slot_len, location, status);
+  if (snap)
+    hipLaunchKernelGGL(index_get_kernel<true>, dim3(g), dim3(kGetBlock), 0, st, view, keys, key_off, key_len, n,
+                       verify_header, multipart_required, stored_off, avail, svc, size, checksum, checksum_initial,
+                       slot_len, location, status);
+  else
+    hipLaunchKernelGGL(index_get_kernel<false>, dim3(g), dim3(kGetBlock), 0, st, view, keys, key_off, key_len, n,
+                       verify_header, multipart_required, stored_off, avail, svc, size, checksum, checksum_initial,
+                       slot_len, location, status);
   e = hipGetLastError();
   if (e == hipSuccess) e = launch_exclusive_scan(st, slot_len, n, out_off, summary + 1);
   if (e != hipSuccess) return hip_code(e);
@@ -1134,6 +1187,19 @@ extern "C" int kdb_index_get_batch(const kdb_index* ix, void* stream, const uint
   hipLaunchKernelGGL(index_summary_kernel, dim3(sg), dim3(256), 0, st, avail, size, status, n,
                      reinterpret_cast<unsigned long long*>(summary));
   return hip_code(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" int kdb_index_get_batch(const kdb_index* ix, void* stream, const uint8_t* keys, const uint64_t* key_off,
+                                   const uint32_t* key_len, uint32_t n, int verify_header,
+                                   uint64_t multipart_required, uint8_t* scratch, uint64_t scratch_bytes,
+                                   uint64_t* stored_off, uint64_t* avail, uint64_t* svc, uint64_t* size,
+                                   uint32_t* checksum, uint32_t* checksum_initial, uint64_t* out_off,
+                                   uint64_t* location, int32_t* status, uint64_t* summary) {
+  return lookup_batch(ix, nullptr, stream, keys, key_off, key_len, n, verify_header, multipart_required, scratch,
+                      scratch_bytes, stored_off, avail, svc, size, checksum, checksum_initial, out_off, location,
+                      status, summary);
 }
 
 // ------------------------------------------------------------------ scan
@@ -1155,14 +1221,21 @@ struct ScanTemps {
   }
 };
 
-IndexView view_of(const kdb_index* ix) {
+// The handle's arrays as they are now; nrows is the handle's row count, or a
+// snapshot's row limit (index_get_kernel<true>, index_live_kernel<true>).
+IndexView view_of(const kdb_index* ix, uint64_t nrows) {
   return IndexView{ix->d_files, ix->d_file_off, ix->d_file_size,        ix->d_fileid, ix->d_start,
-                   ix->d_slots, ix->nbuckets ? ix->nbuckets - 1u : 0u, (uint32_t)ix->nrows, ix->hash_type};
+                   ix->d_slots, ix->nbuckets ? ix->nbuckets - 1u : 0u, (uint32_t)nrows, ix->hash_type};
 }
 
-hipError_t scan_prepare(kdb_index* ix, hipStream_t st, int verify_header, uint64_t* stats_out) {
+// The liveness pass and the ordered list over the handle's first nrows rows,
+// into `sc`: all the handle's rows for its own scan (limited = false), a
+// snapshot's for the snapshot's.  The rank tables are the handle's current
+// ones: the ranks of loaded files do not move.
+hipError_t scan_prepare(const kdb_index* ix, ScanState* sc, uint64_t nrows, bool limited, hipStream_t st,
+                        int verify_header, uint64_t* stats_out) {
   ScanTemps t;
-  const uint32_t n = (uint32_t)ix->nrows;
+  const uint32_t n = (uint32_t)nrows;
   unsigned long long stats[3] = {0, 0, 0};
   uint64_t live = 0;
   if (n) {
@@ -1174,8 +1247,12 @@ hipError_t scan_prepare(kdb_index* ix, hipStream_t st, int verify_header, uint64
     const RowView rows{ix->d_row_hash, ix->d_row_off, ix->d_row_file, ix->d_file_rank};
     const uint32_t waves = kGetBlock / 64;
     const uint32_t g = std::min<uint32_t>((n + waves - 1u) / waves, 16384u);
-    hipLaunchKernelGGL(index_live_kernel, dim3(g), dim3(kGetBlock), 0, st, view_of(ix), rows, verify_header,
-                       t.d_flag, t.d_klen, t.d_stats);
+    if (limited)
+      hipLaunchKernelGGL(index_live_kernel<true>, dim3(g), dim3(kGetBlock), 0, st, view_of(ix, nrows), rows,
+                         verify_header, t.d_flag, t.d_klen, t.d_stats);
+    else
+      hipLaunchKernelGGL(index_live_kernel<false>, dim3(g), dim3(kGetBlock), 0, st, view_of(ix, nrows), rows,
+                         verify_header, t.d_flag, t.d_klen, t.d_stats);
     KDB_TRY(hipGetLastError());
     KDB_TRY(launch_exclusive_scan(st, t.d_flag, n, t.d_pos, t.d_pos + n));
     KDB_TRY(hipMemcpyAsync(&live, t.d_pos + n, 8, hipMemcpyDeviceToHost, st));
@@ -1189,36 +1266,36 @@ hipError_t scan_prepare(kdb_index* ix, hipStream_t st, int verify_header, uint64
       cap = 2;
       while (cap < live) cap <<= 1;
     }
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&ix->d_live), std::max<uint64_t>(cap, 1) * 8u));
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&sc->d_live), std::max<uint64_t>(cap, 1) * 8u));
     KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_list_klen), std::max<uint64_t>(cap, 1) * 4u));
     if (cap > live) {
-      KDB_TRY(hipMemsetAsync(ix->d_live, 0xFF, cap * 8u, st));
+      KDB_TRY(hipMemsetAsync(sc->d_live, 0xFF, cap * 8u, st));
       KDB_TRY(hipMemsetAsync(t.d_list_klen, 0, cap * 4u, st));
     }
     const uint32_t sg = std::min<uint32_t>((n + 255u) / 256u, 2048u);
     hipLaunchKernelGGL(index_live_scatter_kernel, dim3(sg), dim3(256), 0, st, rows, n, t.d_flag, t.d_klen, t.d_pos,
-                       ix->d_live, t.d_list_klen);
+                       sc->d_live, t.d_list_klen);
     KDB_TRY(hipGetLastError());
     if (cap > live || (stats[0] && live > 1)) {
       const uint32_t m = (uint32_t)cap;
       const uint32_t bg = std::min<uint32_t>((m + 255u) / 256u, 2048u);
       for (uint32_t k = 2; k != 0 && k <= m; k <<= 1)
         for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-          hipLaunchKernelGGL(index_bitonic_kernel, dim3(bg), dim3(256), 0, st, ix->d_live, t.d_list_klen, m, k, j);
-          ix->sort_steps++;
+          hipLaunchKernelGGL(index_bitonic_kernel, dim3(bg), dim3(256), 0, st, sc->d_live, t.d_list_klen, m, k, j);
+          sc->sort_steps++;
         }
       KDB_TRY(hipGetLastError());
     }
   }
-  ix->live = live;
-  ix->key_prefix.assign((size_t)live + 1u, 0);
-  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&ix->d_key_prefix), ((size_t)live + 1u) * 8u));
+  sc->live = live;
+  sc->key_prefix.assign((size_t)live + 1u, 0);
+  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&sc->d_key_prefix), ((size_t)live + 1u) * 8u));
   if (live) {
-    KDB_TRY(launch_exclusive_scan(st, t.d_list_klen, (uint32_t)live, ix->d_key_prefix, ix->d_key_prefix + live));
-    KDB_TRY(hipMemcpyAsync(ix->key_prefix.data(), ix->d_key_prefix, ((size_t)live + 1u) * 8u,
+    KDB_TRY(launch_exclusive_scan(st, t.d_list_klen, (uint32_t)live, sc->d_key_prefix, sc->d_key_prefix + live));
+    KDB_TRY(hipMemcpyAsync(sc->key_prefix.data(), sc->d_key_prefix, ((size_t)live + 1u) * 8u,
                            hipMemcpyDeviceToHost, st));
   } else {
-    KDB_TRY(hipMemsetAsync(ix->d_key_prefix, 0, 8, st));
+    KDB_TRY(hipMemsetAsync(sc->d_key_prefix, 0, 8, st));
   }
   KDB_TRY(hipStreamSynchronize(st));
   stats_out[0] = live;
@@ -1227,33 +1304,72 @@ hipError_t scan_prepare(kdb_index* ix, hipStream_t st, int verify_header, uint64
   return hipSuccess;
 }
 
-}  // namespace
-
-extern "C" int kdb_index_scan_prepare(kdb_index* ix, void* stream, int verify_header, uint64_t* live,
-                                      uint64_t* key_bytes, uint32_t* max_key_len) {
-  if (!ix || verify_header < 0 || verify_header > 1) return KDB_PUT_EINVAL;
-  scan_release(ix);
+// kdb_index_scan_prepare and kdb_snapshot_scan_prepare.
+int scan_prepare_checked(const kdb_index* ix, ScanState* sc, uint64_t nrows, bool limited, void* stream,
+                         int verify_header, uint64_t* live, uint64_t* key_bytes, uint32_t* max_key_len) {
+  scan_release(sc);
   uint64_t stats[3] = {0, 0, 0};
-  const hipError_t e = scan_prepare(ix, (hipStream_t)stream, verify_header, stats);
+  const hipError_t e = scan_prepare(ix, sc, nrows, limited, (hipStream_t)stream, verify_header, stats);
   if (e != hipSuccess) {
-    scan_release(ix);
+    scan_release(sc);
     return hip_code(e);
   }
   // the list's own sum of key lengths and the liveness pass's must agree
-  if (ix->key_prefix.back() != stats[1]) {
-    scan_release(ix);
+  if (sc->key_prefix.back() != stats[1]) {
+    scan_release(sc);
     return KDB_PUT_EHIP;
   }
-  ix->scan_ready = true;
+  sc->ready = true;
   if (live) *live = stats[0];
   if (key_bytes) *key_bytes = stats[1];
   if (max_key_len) *max_key_len = (uint32_t)stats[2];
   return KDB_PUT_OK;
 }
 
+// kdb_index_scan_batch and kdb_snapshot_scan_batch: a window of the list `sc`
+// holds, read through the handle's current arrays.
+int scan_batch(const kdb_index* ix, const ScanState* sc, uint64_t nrows, void* stream, uint64_t first, uint32_t n,
+               uint64_t multipart_required, void* scratch, uint64_t scratch_bytes, uint8_t* keys_out,
+               uint64_t keys_cap, uint64_t* key_off, uint32_t* key_len, uint64_t* stored_off, uint64_t* avail,
+               uint64_t* svc, uint64_t* size, uint32_t* checksum, uint32_t* checksum_initial, uint64_t* out_off,
+               uint64_t* location, int32_t* status, uint64_t* summary) {
+  if (multipart_required == 0) multipart_required = 1048576u;    // internal__size_multipart_required
+  if (!ix || !sc->ready || !summary || first > sc->live || n > sc->live - first ||
+      scratch_bytes < kdb_index_scan_scratch_bytes(n) ||
+      (n && (!scratch || !keys_out || !key_off || !key_len || !stored_off || !avail || !svc || !size || !checksum ||
+             !checksum_initial || !out_off || !location || !status)))
+    return KDB_PUT_EINVAL;
+  if (sc->key_prefix[first + n] - sc->key_prefix[first] > keys_cap) return KDB_PUT_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(summary, 0, 5 * 8, st);
+  if (e != hipSuccess) return hip_code(e);
+  if (n == 0) return KDB_PUT_OK;
+  uint32_t* slot_len = reinterpret_cast<uint32_t*>(scratch);
+  const uint32_t waves = kGetBlock / 64;
+  const uint32_t g = std::min<uint32_t>((n + waves - 1u) / waves, 16384u);
+  hipLaunchKernelGGL(index_scan_emit_kernel, dim3(g), dim3(kGetBlock), 0, st, view_of(ix, nrows), sc->d_live,
+                     ix->d_rank_file, sc->d_key_prefix, first, n, multipart_required, keys_out, key_off, key_len,
+                     stored_off, avail, svc, size, checksum, checksum_initial, slot_len, location, status);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = launch_exclusive_scan(st, slot_len, n, out_off, summary + 1);
+  if (e != hipSuccess) return hip_code(e);
+  const uint32_t sg = std::min<uint32_t>((n + 255u) / 256u, 1024u);
+  hipLaunchKernelGGL(index_summary_kernel, dim3(sg), dim3(256), 0, st, avail, size, status, n,
+                     reinterpret_cast<unsigned long long*>(summary));
+  return hip_code(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" int kdb_index_scan_prepare(kdb_index* ix, void* stream, int verify_header, uint64_t* live,
+                                      uint64_t* key_bytes, uint32_t* max_key_len) {
+  if (!ix || verify_header < 0 || verify_header > 1) return KDB_PUT_EINVAL;
+  return scan_prepare_checked(ix, &ix->scan, ix->nrows, false, stream, verify_header, live, key_bytes, max_key_len);
+}
+
 extern "C" int kdb_index_scan_sort_steps(const kdb_index* ix, uint32_t* steps) {
-  if (!ix || !steps || !ix->scan_ready) return KDB_PUT_EINVAL;
-  *steps = ix->sort_steps;
+  if (!ix || !steps || !ix->scan.ready) return KDB_PUT_EINVAL;
+  *steps = ix->scan.sort_steps;
   return KDB_PUT_OK;
 }
 
@@ -1265,28 +1381,83 @@ extern "C" int kdb_index_scan_batch(const kdb_index* ix, void* stream, uint64_t 
                                     uint64_t* stored_off, uint64_t* avail, uint64_t* svc, uint64_t* size,
                                     uint32_t* checksum, uint32_t* checksum_initial, uint64_t* out_off,
                                     uint64_t* location, int32_t* status, uint64_t* summary) {
-  if (multipart_required == 0) multipart_required = 1048576u;    // internal__size_multipart_required
-  if (!ix || !ix->scan_ready || !summary || first > ix->live || n > ix->live - first ||
-      scratch_bytes < kdb_index_scan_scratch_bytes(n) ||
-      (n && (!scratch || !keys_out || !key_off || !key_len || !stored_off || !avail || !svc || !size || !checksum ||
-             !checksum_initial || !out_off || !location || !status)))
-    return KDB_PUT_EINVAL;
-  if (ix->key_prefix[first + n] - ix->key_prefix[first] > keys_cap) return KDB_PUT_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(summary, 0, 5 * 8, st);
-  if (e != hipSuccess) return hip_code(e);
-  if (n == 0) return KDB_PUT_OK;
-  uint32_t* slot_len = reinterpret_cast<uint32_t*>(scratch);
-  const uint32_t waves = kGetBlock / 64;
-  const uint32_t g = std::min<uint32_t>((n + waves - 1u) / waves, 16384u);
-  hipLaunchKernelGGL(index_scan_emit_kernel, dim3(g), dim3(kGetBlock), 0, st, view_of(ix), ix->d_live,
-                     ix->d_rank_file, ix->d_key_prefix, first, n, multipart_required, keys_out, key_off, key_len,
-                     stored_off, avail, svc, size, checksum, checksum_initial, slot_len, location, status);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = launch_exclusive_scan(st, slot_len, n, out_off, summary + 1);
-  if (e != hipSuccess) return hip_code(e);
-  const uint32_t sg = std::min<uint32_t>((n + 255u) / 256u, 1024u);
-  hipLaunchKernelGGL(index_summary_kernel, dim3(sg), dim3(256), 0, st, avail, size, status, n,
-                     reinterpret_cast<unsigned long long*>(summary));
-  return hip_code(hipGetLastError());
+  if (!ix) return KDB_PUT_EINVAL;
+  return scan_batch(ix, &ix->scan, ix->nrows, stream, first, n, multipart_required, scratch, scratch_bytes, keys_out,
+                    keys_cap, key_off, key_len, stored_off, avail, svc, size, checksum, checksum_initial, out_off,
+                    location, status, summary);
+}
+
+// ------------------------------------------------------------------ snapshot
+// Database::NewSnapshot (interface/database.cc:301-327): host bookkeeping alone.
+extern "C" int kdb_snapshot_create(kdb_index* ix, kdb_snapshot** snap) {
+  if (!ix || !snap || ix->snapshots == 0xFFFFFFFFu) return KDB_PUT_EINVAL;
+  kdb_snapshot* p = new (std::nothrow) kdb_snapshot;
+  if (!p) return KDB_PUT_EINVAL;
+  p->ix = ix;
+  p->nrows = ix->nrows;
+  p->nfiles = ix->nfiles;
+  p->nloaded = ix->nloaded;
+  ix->snapshots++;
+  *snap = p;
+  return KDB_PUT_OK;
+}
+
+// Snapshot::Close (interface/snapshot.h:67-76)
+extern "C" int kdb_snapshot_release(kdb_snapshot* snap) {
+  if (!snap) return KDB_PUT_EINVAL;
+  scan_release(&snap->scan);
+  snap->ix->snapshots--;
+  delete snap;
+  return KDB_PUT_OK;
+}
+
+extern "C" int kdb_snapshot_entry_count(const kdb_snapshot* snap, uint64_t* count) {
+  if (!snap || !count) return KDB_PUT_EINVAL;
+  *count = snap->nrows;
+  return KDB_PUT_OK;
+}
+
+extern "C" int kdb_snapshot_file_count(const kdb_snapshot* snap, uint32_t* count) {
+  if (!snap || !count) return KDB_PUT_EINVAL;
+  *count = snap->nfiles;
+  return KDB_PUT_OK;
+}
+
+// Snapshot::Get (interface/snapshot.h:78-92)
+extern "C" int kdb_snapshot_get_batch(const kdb_snapshot* snap, void* stream, const uint8_t* keys,
+                                      const uint64_t* key_off, const uint32_t* key_len, uint32_t n,
+                                      int verify_header, uint64_t multipart_required, uint8_t* scratch,
+                                      uint64_t scratch_bytes, uint64_t* stored_off, uint64_t* avail, uint64_t* svc,
+                                      uint64_t* size, uint32_t* checksum, uint32_t* checksum_initial,
+                                      uint64_t* out_off, uint64_t* location, int32_t* status, uint64_t* summary) {
+  if (!snap) return KDB_PUT_EINVAL;
+  return lookup_batch(snap->ix, snap, stream, keys, key_off, key_len, n, verify_header, multipart_required, scratch,
+                      scratch_bytes, stored_off, avail, svc, size, checksum, checksum_initial, out_off, location,
+                      status, summary);
+}
+
+// Snapshot::NewIterator (interface/snapshot.h:110-121)
+extern "C" int kdb_snapshot_scan_prepare(kdb_snapshot* snap, void* stream, int verify_header, uint64_t* live,
+                                         uint64_t* key_bytes, uint32_t* max_key_len) {
+  if (!snap || verify_header < 0 || verify_header > 1) return KDB_PUT_EINVAL;
+  return scan_prepare_checked(snap->ix, &snap->scan, snap->nrows, true, stream, verify_header, live, key_bytes,
+                              max_key_len);
+}
+
+extern "C" int kdb_snapshot_scan_sort_steps(const kdb_snapshot* snap, uint32_t* steps) {
+  if (!snap || !steps || !snap->scan.ready) return KDB_PUT_EINVAL;
+  *steps = snap->scan.sort_steps;
+  return KDB_PUT_OK;
+}
+
+extern "C" int kdb_snapshot_scan_batch(const kdb_snapshot* snap, void* stream, uint64_t first, uint32_t n,
+                                       uint64_t multipart_required, void* scratch, uint64_t scratch_bytes,
+                                       uint8_t* keys_out, uint64_t keys_cap, uint64_t* key_off, uint32_t* key_len,
+                                       uint64_t* stored_off, uint64_t* avail, uint64_t* svc, uint64_t* size,
+                                       uint32_t* checksum, uint32_t* checksum_initial, uint64_t* out_off,
+                                       uint64_t* location, int32_t* status, uint64_t* summary) {
+  if (!snap) return KDB_PUT_EINVAL;
+  return scan_batch(snap->ix, &snap->scan, snap->nrows, stream, first, n, multipart_required, scratch, scratch_bytes,
+                    keys_out, keys_cap, key_off, key_len, stored_off, avail, svc, size, checksum, checksum_initial,
+                    out_off, location, status, summary);
 }

@@ -19,6 +19,9 @@ set of closed HSTable files and the batched lookup in front of the decoder.
   .refresh()              adds the files the writer has closed since
                           (kdb_index_add_files; StorageEngine::ProcessingLoopIndex):
                           write -> refresh -> get, with no file loaded twice
+  .snapshot()             an HSTableSnapshot: get, locate, scan, items, compacted
+                          and compacted_device as of now, while refresh() and
+                          add_files() go on (kdb_snapshot_*; Database::NewSnapshot)
   HSTableIndex(files, reserve=N) / .add_files(files)
                           the same for an uploaded index: new files go into
                           the N spare bytes behind the first ones
@@ -93,7 +96,318 @@ class _Borrowed:
         pass
 
 
-class HSTableIndex:
+class _ReadPath:
+    """The read path of HSTableIndex and HSTableSnapshot: the lookup, the scan
+    windows, their decode and the compaction, over `self.h` through the C
+    entry points `<_ABI>_get_batch`, `<_ABI>_scan_prepare`,
+    `<_ABI>_scan_sort_steps` and `<_ABI>_scan_batch`.  A subclass sets _ABI
+    and provides h, files, hash_type and _scan (None: no scan prepared)."""
+
+    _ABI = "kdb_index"
+
+    def _call(self, name: str, *args) -> None:
+        name = f"{self._ABI}_{name}"
+        _lib.check(getattr(lib(), name)(self.h, *args), name)
+
+    def _lookup(self, keys, st, verify_header: int, multipart_required: int) -> _Lookup:
+        n = len(keys)
+        klen = np.array([len(k) for k in keys], np.uint32)
+        koff = np.zeros(n, np.uint64)
+        if n > 1:
+            koff[1:] = np.cumsum(klen[:-1].astype(np.uint64))
+        kbuf = np.frombuffer(b"".join(keys), np.uint8)
+        L = _Lookup(n, len(kbuf))
+        try:
+            if len(kbuf):
+                L.keys.upload(kbuf, stream=st)
+            L.meta.upload(koff, L.off["key_off"], stream=st)
+            L.meta.upload(klen, L.off["key_len"], stream=st)
+            self.run_lookup(L, st, n, verify_header, multipart_required)
+        except Exception:
+            L.free()
+            raise
+        return L
+
+    def run_lookup(self, L: _Lookup, st, n: int, verify_header: int = 0,
+                   multipart_required: int = MULTIPART_REQUIRED) -> None:
+        """kdb_index_get_batch / kdb_snapshot_get_batch on keys already resident in `L`."""
+        self._call(
+            "get_batch", st, L.keys.ptr, L.p("key_off"), L.p("key_len"), n, verify_header, multipart_required,
+            L.scratch.ptr, L.scratch_bytes, L.p("stored_off"), L.p("avail"), L.p("svc"), L.p("size"),
+            L.p("checksum"), L.p("checksum_initial"), L.p("out_off"), L.p("location"), L.p("status"),
+            L.p("summary"))
+
+    def decode_plan(self, L: _Lookup, st, n: int, frame_cap: int | None = None):
+        """The summary download: (found, out bytes, frame_cap, max_in, max_out)."""
+        s = L.meta.download(40, L.off["summary"], dtype=np.uint64, stream=st)
+        found, out_bytes, max_avail, max_size, slots = (int(x) for x in s)
+        if frame_cap is None:
+            # frames are >= 8 bytes, so `slots` always suffices; values KingDB
+            # writes hold one frame per part, far fewer (see get.get_values)
+            frame_cap = min(slots, 2 * n + 8 * (slots - n) // 4096 + 64)
+        return found, out_bytes, frame_cap, max_avail, max_size
+
+    def run_decode(self, L: _Lookup, st, n: int, verify: int, out: DeviceBuffer, scratch: DeviceBuffer,
+                   frame_cap: int, max_in: int, max_out: int) -> None:
+        _lib.check(lib().kdb_get_values_batch(
+            st, self.files.ptr, L.p("stored_off"), L.p("avail"), L.p("svc"), L.p("size"), n, out.ptr,
+            L.p("out_off"), verify, L.p("checksum"), L.p("checksum_initial"), frame_cap, max_in, max_out,
+            scratch.ptr, scratch.nbytes, L.p("out_len"), L.p("dstatus")), "kdb_get_values_batch")
+
+    def locate(self, keys, verify_header: int = 0, stream: Stream | None = None,
+               multipart_required: int = MULTIPART_REQUIRED) -> tuple[np.ndarray, np.ndarray]:
+        n = len(keys)
+        if n == 0:
+            return np.zeros(0, np.uint64), np.zeros(0, np.int32)
+        st = stream.ptr if stream else None
+        L = self._lookup(keys, st, verify_header, multipart_required)
+        try:
+            loc = L.meta.download(8 * n, L.off["location"], dtype=np.uint64, stream=st)
+            status = L.meta.download(4 * n, L.off["status"], dtype=np.int32, stream=st)
+            return loc, status
+        finally:
+            L.free()
+
+    def get(self, keys, verify: int = 0, stream: Stream | None = None,
+            multipart_required: int = MULTIPART_REQUIRED, frame_cap: int | None = None
+            ) -> list[tuple[int, bytes]]:
+        n = len(keys)
+        if n == 0:
+            return []
+        st = stream.ptr if stream else None
+        L = self._lookup(keys, st, 1 if verify else 0, multipart_required)
+        out = scratch = None
+        try:
+            found, out_bytes, frame_cap, max_in, max_out = self.decode_plan(L, st, n, frame_cap)
+            status = L.meta.download(4 * n, L.off["status"], dtype=np.int32, stream=st)
+            if found == 0:
+                return [(int(s), b"") for s in status]
+            out = DeviceBuffer(out_bytes + 64)
+            scratch = DeviceBuffer(int(lib().kdb_get_scratch_bytes(n, frame_cap)))
+            self.run_decode(L, st, n, verify, out, scratch, frame_cap, max_in, max_out)
+            lo, hi = L.off["out_off"], L.off["out_len"] + 8 * n
+            m = L.meta.download(hi - lo, lo, stream=st)
+            ooff = m[:8 * n].view(np.uint64)
+            olen = m[L.off["out_len"] - lo:][:8 * n].view(np.uint64)
+            dstatus = L.meta.download(4 * n, L.off["dstatus"], dtype=np.int32, stream=st)
+            data = out.download(out_bytes, stream=st)
+            res = []
+            for i in range(n):
+                if status[i] != 0:
+                    res.append((int(status[i]), b""))
+                else:
+                    res.append((int(dstatus[i]), data[int(ooff[i]):int(ooff[i]) + int(olen[i])].tobytes()))
+            return res
+        finally:
+            L.free()
+            for b in (out, scratch):
+                if b is not None:
+                    b.free()
+
+    # ------------------------------------------------------------------ scan
+    def scan_prepare(self, verify: int = 0, stream: Stream | None = None) -> int:
+        """The liveness pass and the ordered live list (kdb_index_scan_prepare):
+        the number of live entries.  Implicit on the first scan and repeated
+        when `verify` changes (the header CRC-8 is part of liveness)."""
+        live, kbytes, kmax = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+        self._scan = None
+        self._call("scan_prepare", stream.ptr if stream else None, 1 if verify else 0, ctypes.byref(live),
+                   ctypes.byref(kbytes), ctypes.byref(kmax))
+        self._scan = (1 if verify else 0, live.value, kbytes.value, kmax.value)
+        return live.value
+
+    def _prepared(self, verify: int, stream: Stream | None) -> tuple[int, int, int]:
+        s = self._scan
+        if s is None or s[0] != (1 if verify else 0):
+            self.scan_prepare(verify, stream)
+        return self._scan[1:]
+
+    def scan_sort_steps(self) -> int:
+        """Compare-exchange passes the last scan_prepare ran (0: the files' rows ascend)."""
+        steps = ctypes.c_uint32(0)
+        self._call("scan_sort_steps", ctypes.byref(steps))
+        return steps.value
+
+    def run_scan(self, L: _Lookup, st, first: int, n: int, multipart_required: int = MULTIPART_REQUIRED) -> None:
+        """kdb_index_scan_batch / kdb_snapshot_scan_batch into `L` (its keys buffer takes the packed keys)."""
+        self._call(
+            "scan_batch", st, first, n, multipart_required, L.scratch.ptr, L.scratch_bytes, L.keys.ptr, L.keys.nbytes,
+            L.p("key_off"), L.p("key_len"), L.p("stored_off"), L.p("avail"), L.p("svc"), L.p("size"),
+            L.p("checksum"), L.p("checksum_initial"), L.p("out_off"), L.p("location"), L.p("status"),
+            L.p("summary"))
+
+    def scan(self, first: int = 0, count: int | None = None, verify: int = 0,
+             multipart_required: int = MULTIPART_REQUIRED, stream: Stream | None = None,
+             frame_cap: int | None = None) -> list[tuple[bytes, int, bytes]]:
+        """One window [first, first + count) of the live entries in iterator
+        order (files by (timestamp, fileid), offsets ascending):
+        [(key, status, value)], values decoded by kdb_get_values_batch.  status
+        is 0, MULTIPART (value b"") or the decoder's -1 / -2."""
+        live, _, kmax = self._prepared(verify, stream)
+        n = live - first if count is None else count
+        if first < 0 or n < 0 or first + n > live:
+            raise _lib.HipError(f"scan window [{first}, {first + n}) outside the {live} live entries")
+        if n == 0:
+            return []
+        st = stream.ptr if stream else None
+        L = _Lookup(n, n * kmax)
+        out = scratch = None
+        try:
+            self.run_scan(L, st, first, n, multipart_required)
+            found, out_bytes, frame_cap, max_in, max_out = self.decode_plan(L, st, n, frame_cap)
+            lo, hi = L.off["key_off"], L.off["key_off"] + 8 * n
+            koff = L.meta.download(hi - lo, lo, dtype=np.uint64, stream=st)
+            klen = L.meta.download(4 * n, L.off["key_len"], dtype=np.uint32, stream=st)
+            status = L.meta.download(4 * n, L.off["status"], dtype=np.int32, stream=st)
+            kbytes = int(koff[-1]) + int(klen[-1])
+            kdata = L.keys.download(kbytes, stream=st) if kbytes else np.zeros(0, np.uint8)
+            keys = [kdata[int(o):int(o) + int(m)].tobytes() for o, m in zip(koff, klen)]
+            if found == 0:
+                return [(k, int(s), b"") for k, s in zip(keys, status)]
+            out = DeviceBuffer(out_bytes + 64)
+            scratch = DeviceBuffer(int(lib().kdb_get_scratch_bytes(n, frame_cap)))
+            self.run_decode(L, st, n, verify, out, scratch, frame_cap, max_in, max_out)
+            ooff = L.meta.download(8 * n, L.off["out_off"], dtype=np.uint64, stream=st)
+            olen = L.meta.download(8 * n, L.off["out_len"], dtype=np.uint64, stream=st)
+            dstatus = L.meta.download(4 * n, L.off["dstatus"], dtype=np.int32, stream=st)
+            data = out.download(out_bytes, stream=st)
+            res = []
+            for i in range(n):
+                if status[i] != 0:
+                    res.append((keys[i], int(status[i]), b""))
+                else:
+                    res.append((keys[i], int(dstatus[i]), data[int(ooff[i]):int(ooff[i]) + int(olen[i])].tobytes()))
+            return res
+        finally:
+            L.free()
+            for b in (out, scratch):
+                if b is not None:
+                    b.free()
+
+    def items(self, batch: int = 65536, verify: int = 0, multipart_required: int = MULTIPART_REQUIRED,
+              stream: Stream | None = None):
+        """Generator over every live entry, a window of `batch` at a time, so a
+        large database never has all its values in memory at once."""
+        live, _, _ = self._prepared(verify, stream)
+        for first in range(0, live, max(batch, 1)):
+            yield from self.scan(first, min(batch, live - first), verify, multipart_required, stream)
+
+    def compacted(self, hstable_size: int = 32 << 20, batch: int = 65536, verify: int = 0) -> dict[str, bytes]:
+        """An offline compaction: the live entries (every key once, no deletes,
+        no overwritten entries) written again through put.write_hstables, a
+        window of the scan per write-buffer flush.  The files are an ordinary
+        database holding exactly the live entries; this does not claim the
+        file layout the reference's own compaction produces."""
+        from . import put
+        w = put.HSTableWriter(hstable_size, self.hash_type)
+        window = []
+        for key, status, value in self.items(batch, verify, multipart_required=1 << 62):
+            if status != 0:
+                raise _lib.HipError(f"compacted: value of {key!r} does not decode (status {status})")
+            window.append((key, value))
+            if len(window) == batch:
+                w.append(put.put_entries(window, self.hash_type))
+                window = []
+        if window:
+            w.append(put.put_entries(window, self.hash_type))
+        w.close()
+        return w.files()
+
+    def compacted_device(self, hstable_size: int = 32 << 20, batch: int = 65536, verify: int = 0):
+        """compacted() with no value byte leaving device memory: a closed
+        put.DeviceHSTableWriter holding, batch for batch, the files
+        compacted() returns (`.files()` downloads them, from_resident() opens
+        them in place).  Each scan window's decode outputs are the inputs of
+        kdb_put_entries_batch as they lie -- the packed keys, the decode buffer
+        with out_off / out_len as value_off / value_len -- and the entries go
+        to the device writer.  Per window the host sees the 40-byte summary,
+        one flag and the writer's plan."""
+        from . import put
+        batch = max(batch, 1)
+        live, kbytes, kmax = self._prepared(verify, None)
+        windows = [(first, min(batch, live - first)) for first in range(0, live, batch)]
+        big = 1 << 62
+        # sizing pass: the window summaries alone bound the entry bytes
+        bound = 0
+        for first, n in windows:
+            L = _Lookup(n, n * kmax)
+            try:
+                self.run_scan(L, None, first, n, big)
+                _, out_bytes, _, _, _ = self.decode_plan(L, None, n)
+            finally:
+                L.free()
+            bound += out_bytes + n * (72 + kmax) + (out_bytes // 65536 + n + 1) * 16 + 64
+        w = put.DeviceHSTableWriter(hstable_size, self.hash_type,
+                                    put.DeviceHSTableWriter.arena_bytes(hstable_size, bound, live))
+        try:
+            for first, n in windows:
+                self._compact_window(w, first, n, kmax, verify, big)
+            w.close()
+        except Exception:
+            w.free()
+            raise
+        return w
+
+    def _compact_window(self, w, first: int, n: int, kmax: int, verify: int, big: int) -> None:
+        from . import put
+        L = _Lookup(n, n * kmax)
+        bufs = [L]
+        try:
+            self.run_scan(L, None, first, n, big)
+            found, out_bytes, frame_cap, max_in, max_out = self.decode_plan(L, None, n)
+            if found != n:
+                self._compact_fail(L, n, False)
+            out = DeviceBuffer(out_bytes + 64)
+            bufs.append(out)
+            scratch = DeviceBuffer(int(lib().kdb_get_scratch_bytes(n, frame_cap)))
+            bufs.append(scratch)
+            self.run_decode(L, None, n, verify, out, scratch, frame_cap, max_in, max_out)
+            # part_first u32 (n + 1), chunk_len u32 (n), flag u32
+            feed = DeviceBuffer(_a8(4 * (n + 1)) + _a8(4 * n) + 8)
+            bufs.append(feed)
+            part_first, chunk_len = feed.ptr, feed.ptr + _a8(4 * (n + 1))
+            flag = chunk_len + _a8(4 * n)
+            _lib.check(lib().kdb_hstable_dev_feed(None, L.p("out_len"), L.p("status"), L.p("dstatus"), n, part_first,
+                                                  chunk_len, flag), "kdb_hstable_dev_feed")
+            raw = max(out_bytes, 1)
+            pscratch_bytes = int(lib().kdb_put_scratch_bytes(n, n, raw))
+            pscratch = DeviceBuffer(pscratch_bytes)
+            bufs.append(pscratch)
+            entries = DeviceBuffer(raw + n * (72 + kmax) + (raw // 65536 + n + 1) * 16 + 64)
+            bufs.append(entries)
+            po = DeviceBuffer(n * 32 + 64)
+            bufs.append(po)
+            o = po.ptr
+            e_off, e_len, hashed, crc, kind, status, total = (o, o + 8 * n, o + 12 * n, o + 20 * n, o + 24 * n,
+                                                              o + 28 * n, o + 32 * n)
+            _lib.check(lib().kdb_put_entries_batch(
+                None, L.keys.ptr, L.p("key_off"), L.p("key_len"), out.ptr, L.p("out_off"), L.p("out_len"), part_first,
+                chunk_len, n, max_out, n, self.hash_type, pscratch.ptr, pscratch_bytes, raw, entries.ptr, e_off,
+                e_len, total, hashed, crc, kind, status), "kdb_put_entries_batch")
+            if int(feed.download(4, flag - feed.ptr, dtype=np.uint32)[0]):
+                self._compact_fail(L, n, True)
+            w.append_ptrs(None, entries.ptr, e_off, e_len, hashed, kind, status, n)
+            _lib.check(lib().kdb_lz4_stream_sync(None), "sync")     # the window's buffers are read by queued work
+        finally:
+            for b in bufs:
+                b.free()
+
+    def _compact_fail(self, L: _Lookup, n: int, decoded: bool) -> None:
+        """The error compacted() raises, for the window's first value that does not decode."""
+        status = L.meta.download(4 * n, L.off["status"], dtype=np.int32)
+        dstatus = L.meta.download(4 * n, L.off["dstatus"], dtype=np.int32) if decoded else status
+        koff = L.meta.download(8 * n, L.off["key_off"], dtype=np.uint64)
+        klen = L.meta.download(4 * n, L.off["key_len"], dtype=np.uint32)
+        for i in range(n):
+            s = int(status[i]) or int(dstatus[i])
+            if s:
+                key = L.keys.download(int(klen[i]), int(koff[i])).tobytes() if klen[i] else b""
+                raise _lib.HipError(f"compacted: value of {key!r} does not decode (status {s})")
+        raise _lib.HipError("compacted: a value of the window does not decode")
+
+
+class HSTableIndex(_ReadPath):
+    _snapshots = None                    # the open HSTableSnapshots, once there was one
     def __init__(self, files: dict[str, bytes], hash_type: int = 1, stream: Stream | None = None,
                  recover: str | None = None, reserve: int = 0):
         from . import recover as rec
@@ -297,308 +611,78 @@ class HSTableIndex:
         _lib.check(lib().kdb_index_pairs(self.h, h.ctypes.data, loc.ctypes.data), "kdb_index_pairs")
         return h[:self.entries], loc[:self.entries]
 
-    def _lookup(self, keys, st, verify_header: int, multipart_required: int) -> _Lookup:
-        n = len(keys)
-        klen = np.array([len(k) for k in keys], np.uint32)
-        koff = np.zeros(n, np.uint64)
-        if n > 1:
-            koff[1:] = np.cumsum(klen[:-1].astype(np.uint64))
-        kbuf = np.frombuffer(b"".join(keys), np.uint8)
-        L = _Lookup(n, len(kbuf))
-        try:
-            if len(kbuf):
-                L.keys.upload(kbuf, stream=st)
-            L.meta.upload(koff, L.off["key_off"], stream=st)
-            L.meta.upload(klen, L.off["key_len"], stream=st)
-            self.run_lookup(L, st, n, verify_header, multipart_required)
-        except Exception:
-            L.free()
-            raise
-        return L
-
-    def run_lookup(self, L: _Lookup, st, n: int, verify_header: int = 0,
-                   multipart_required: int = MULTIPART_REQUIRED) -> None:
-        """kdb_index_get_batch on keys already resident in `L`."""
-        _lib.check(lib().kdb_index_get_batch(
-            self.h, st, L.keys.ptr, L.p("key_off"), L.p("key_len"), n, verify_header, multipart_required,
-            L.scratch.ptr, L.scratch_bytes, L.p("stored_off"), L.p("avail"), L.p("svc"), L.p("size"),
-            L.p("checksum"), L.p("checksum_initial"), L.p("out_off"), L.p("location"), L.p("status"),
-            L.p("summary")), "kdb_index_get_batch")
-
-    def decode_plan(self, L: _Lookup, st, n: int, frame_cap: int | None = None):
-        """The summary download: (found, out bytes, frame_cap, max_in, max_out)."""
-        s = L.meta.download(40, L.off["summary"], dtype=np.uint64, stream=st)
-        found, out_bytes, max_avail, max_size, slots = (int(x) for x in s)
-        if frame_cap is None:
-            # frames are >= 8 bytes, so `slots` always suffices; values KingDB
-            # writes hold one frame per part, far fewer (see get.get_values)
-            frame_cap = min(slots, 2 * n + 8 * (slots - n) // 4096 + 64)
-        return found, out_bytes, frame_cap, max_avail, max_size
-
-    def run_decode(self, L: _Lookup, st, n: int, verify: int, out: DeviceBuffer, scratch: DeviceBuffer,
-                   frame_cap: int, max_in: int, max_out: int) -> None:
-        _lib.check(lib().kdb_get_values_batch(
-            st, self.files.ptr, L.p("stored_off"), L.p("avail"), L.p("svc"), L.p("size"), n, out.ptr,
-            L.p("out_off"), verify, L.p("checksum"), L.p("checksum_initial"), frame_cap, max_in, max_out,
-            scratch.ptr, scratch.nbytes, L.p("out_len"), L.p("dstatus")), "kdb_get_values_batch")
-
-    def locate(self, keys, verify_header: int = 0, stream: Stream | None = None,
-               multipart_required: int = MULTIPART_REQUIRED) -> tuple[np.ndarray, np.ndarray]:
-        n = len(keys)
-        if n == 0:
-            return np.zeros(0, np.uint64), np.zeros(0, np.int32)
-        st = stream.ptr if stream else None
-        L = self._lookup(keys, st, verify_header, multipart_required)
-        try:
-            loc = L.meta.download(8 * n, L.off["location"], dtype=np.uint64, stream=st)
-            status = L.meta.download(4 * n, L.off["status"], dtype=np.int32, stream=st)
-            return loc, status
-        finally:
-            L.free()
-
-    def get(self, keys, verify: int = 0, stream: Stream | None = None,
-            multipart_required: int = MULTIPART_REQUIRED, frame_cap: int | None = None
-            ) -> list[tuple[int, bytes]]:
-        n = len(keys)
-        if n == 0:
-            return []
-        st = stream.ptr if stream else None
-        L = self._lookup(keys, st, 1 if verify else 0, multipart_required)
-        out = scratch = None
-        try:
-            found, out_bytes, frame_cap, max_in, max_out = self.decode_plan(L, st, n, frame_cap)
-            status = L.meta.download(4 * n, L.off["status"], dtype=np.int32, stream=st)
-            if found == 0:
-                return [(int(s), b"") for s in status]
-            out = DeviceBuffer(out_bytes + 64)
-            scratch = DeviceBuffer(int(lib().kdb_get_scratch_bytes(n, frame_cap)))
-            self.run_decode(L, st, n, verify, out, scratch, frame_cap, max_in, max_out)
-            lo, hi = L.off["out_off"], L.off["out_len"] + 8 * n
-            m = L.meta.download(hi - lo, lo, stream=st)
-            ooff = m[:8 * n].view(np.uint64)
-            olen = m[L.off["out_len"] - lo:][:8 * n].view(np.uint64)
-            dstatus = L.meta.download(4 * n, L.off["dstatus"], dtype=np.int32, stream=st)
-            data = out.download(out_bytes, stream=st)
-            res = []
-            for i in range(n):
-                if status[i] != 0:
-                    res.append((int(status[i]), b""))
-                else:
-                    res.append((int(dstatus[i]), data[int(ooff[i]):int(ooff[i]) + int(olen[i])].tobytes()))
-            return res
-        finally:
-            L.free()
-            for b in (out, scratch):
-                if b is not None:
-                    b.free()
-
-    # ------------------------------------------------------------------ scan
-    def scan_prepare(self, verify: int = 0, stream: Stream | None = None) -> int:
-        """The liveness pass and the ordered live list (kdb_index_scan_prepare):
-        the number of live entries.  Implicit on the first scan and repeated
-        when `verify` changes (the header CRC-8 is part of liveness)."""
-        live, kbytes, kmax = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
-        self._scan = None
-        _lib.check(lib().kdb_index_scan_prepare(self.h, stream.ptr if stream else None, 1 if verify else 0,
-                                                ctypes.byref(live), ctypes.byref(kbytes), ctypes.byref(kmax)),
-                   "kdb_index_scan_prepare")
-        self._scan = (1 if verify else 0, live.value, kbytes.value, kmax.value)
-        return live.value
-
-    def _prepared(self, verify: int, stream: Stream | None) -> tuple[int, int, int]:
-        s = self._scan
-        if s is None or s[0] != (1 if verify else 0):
-            self.scan_prepare(verify, stream)
-        return self._scan[1:]
-
-    def scan_sort_steps(self) -> int:
-        """Compare-exchange passes the last scan_prepare ran (0: the files' rows ascend)."""
-        steps = ctypes.c_uint32(0)
-        _lib.check(lib().kdb_index_scan_sort_steps(self.h, ctypes.byref(steps)), "kdb_index_scan_sort_steps")
-        return steps.value
-
-    def run_scan(self, L: _Lookup, st, first: int, n: int, multipart_required: int = MULTIPART_REQUIRED) -> None:
-        """kdb_index_scan_batch into `L` (its keys buffer takes the packed keys)."""
-        _lib.check(lib().kdb_index_scan_batch(
-            self.h, st, first, n, multipart_required, L.scratch.ptr, L.scratch_bytes, L.keys.ptr, L.keys.nbytes,
-            L.p("key_off"), L.p("key_len"), L.p("stored_off"), L.p("avail"), L.p("svc"), L.p("size"),
-            L.p("checksum"), L.p("checksum_initial"), L.p("out_off"), L.p("location"), L.p("status"),
-            L.p("summary")), "kdb_index_scan_batch")
-
-    def scan(self, first: int = 0, count: int | None = None, verify: int = 0,
-             multipart_required: int = MULTIPART_REQUIRED, stream: Stream | None = None,
-             frame_cap: int | None = None) -> list[tuple[bytes, int, bytes]]:
-        """One window [first, first + count) of the live entries in iterator
-        order (files by (timestamp, fileid), offsets ascending):
-        [(key, status, value)], values decoded by kdb_get_values_batch.  status
-        is 0, MULTIPART (value b"") or the decoder's -1 / -2."""
-        live, _, kmax = self._prepared(verify, stream)
-        n = live - first if count is None else count
-        if first < 0 or n < 0 or first + n > live:
-            raise _lib.HipError(f"scan window [{first}, {first + n}) outside the {live} live entries")
-        if n == 0:
-            return []
-        st = stream.ptr if stream else None
-        L = _Lookup(n, n * kmax)
-        out = scratch = None
-        try:
-            self.run_scan(L, st, first, n, multipart_required)
-            found, out_bytes, frame_cap, max_in, max_out = self.decode_plan(L, st, n, frame_cap)
-            lo, hi = L.off["key_off"], L.off["key_off"] + 8 * n
-            koff = L.meta.download(hi - lo, lo, dtype=np.uint64, stream=st)
-            klen = L.meta.download(4 * n, L.off["key_len"], dtype=np.uint32, stream=st)
-            status = L.meta.download(4 * n, L.off["status"], dtype=np.int32, stream=st)
-            kbytes = int(koff[-1]) + int(klen[-1])
-            kdata = L.keys.download(kbytes, stream=st) if kbytes else np.zeros(0, np.uint8)
-            keys = [kdata[int(o):int(o) + int(m)].tobytes() for o, m in zip(koff, klen)]
-            if found == 0:
-                return [(k, int(s), b"") for k, s in zip(keys, status)]
-            out = DeviceBuffer(out_bytes + 64)
-            scratch = DeviceBuffer(int(lib().kdb_get_scratch_bytes(n, frame_cap)))
-            self.run_decode(L, st, n, verify, out, scratch, frame_cap, max_in, max_out)
-            ooff = L.meta.download(8 * n, L.off["out_off"], dtype=np.uint64, stream=st)
-            olen = L.meta.download(8 * n, L.off["out_len"], dtype=np.uint64, stream=st)
-            dstatus = L.meta.download(4 * n, L.off["dstatus"], dtype=np.int32, stream=st)
-            data = out.download(out_bytes, stream=st)
-            res = []
-            for i in range(n):
-                if status[i] != 0:
-                    res.append((keys[i], int(status[i]), b""))
-                else:
-                    res.append((keys[i], int(dstatus[i]), data[int(ooff[i]):int(ooff[i]) + int(olen[i])].tobytes()))
-            return res
-        finally:
-            L.free()
-            for b in (out, scratch):
-                if b is not None:
-                    b.free()
-
-    def items(self, batch: int = 65536, verify: int = 0, multipart_required: int = MULTIPART_REQUIRED,
-              stream: Stream | None = None):
-        """Generator over every live entry, a window of `batch` at a time, so a
-        large database never has all its values in memory at once."""
-        live, _, _ = self._prepared(verify, stream)
-        for first in range(0, live, max(batch, 1)):
-            yield from self.scan(first, min(batch, live - first), verify, multipart_required, stream)
-
-    def compacted(self, hstable_size: int = 32 << 20, batch: int = 65536, verify: int = 0) -> dict[str, bytes]:
-        """An offline compaction: the live entries (every key once, no deletes,
-        no overwritten entries) written again through put.write_hstables, a
-        window of the scan per write-buffer flush.  The files are an ordinary
-        database holding exactly the live entries; this does not claim the
-        file layout the reference's own compaction produces."""
-        from . import put
-        w = put.HSTableWriter(hstable_size, self.hash_type)
-        window = []
-        for key, status, value in self.items(batch, verify, multipart_required=1 << 62):
-            if status != 0:
-                raise _lib.HipError(f"compacted: value of {key!r} does not decode (status {status})")
-            window.append((key, value))
-            if len(window) == batch:
-                w.append(put.put_entries(window, self.hash_type))
-                window = []
-        if window:
-            w.append(put.put_entries(window, self.hash_type))
-        w.close()
-        return w.files()
-
-    def compacted_device(self, hstable_size: int = 32 << 20, batch: int = 65536, verify: int = 0):
-        """compacted() with no value byte leaving device memory: a closed
-        put.DeviceHSTableWriter holding, batch for batch, the files
-        compacted() returns (`.files()` downloads them, from_resident() opens
-        them in place).  Each scan window's decode outputs are the inputs of
-        kdb_put_entries_batch as they lie -- the packed keys, the decode buffer
-        with out_off / out_len as value_off / value_len -- and the entries go
-        to the device writer.  Per window the host sees the 40-byte summary,
-        one flag and the writer's plan."""
-        from . import put
-        batch = max(batch, 1)
-        live, kbytes, kmax = self._prepared(verify, None)
-        windows = [(first, min(batch, live - first)) for first in range(0, live, batch)]
-        big = 1 << 62
-        # sizing pass: the window summaries alone bound the entry bytes
-        bound = 0
-        for first, n in windows:
-            L = _Lookup(n, n * kmax)
-            try:
-                self.run_scan(L, None, first, n, big)
-                _, out_bytes, _, _, _ = self.decode_plan(L, None, n)
-            finally:
-                L.free()
-            bound += out_bytes + n * (72 + kmax) + (out_bytes // 65536 + n + 1) * 16 + 64
-        w = put.DeviceHSTableWriter(hstable_size, self.hash_type,
-                                    put.DeviceHSTableWriter.arena_bytes(hstable_size, bound, live))
-        try:
-            for first, n in windows:
-                self._compact_window(w, first, n, kmax, verify, big)
-            w.close()
-        except Exception:
-            w.free()
-            raise
-        return w
-
-    def _compact_window(self, w, first: int, n: int, kmax: int, verify: int, big: int) -> None:
-        from . import put
-        L = _Lookup(n, n * kmax)
-        bufs = [L]
-        try:
-            self.run_scan(L, None, first, n, big)
-            found, out_bytes, frame_cap, max_in, max_out = self.decode_plan(L, None, n)
-            if found != n:
-                self._compact_fail(L, n, False)
-            out = DeviceBuffer(out_bytes + 64)
-            bufs.append(out)
-            scratch = DeviceBuffer(int(lib().kdb_get_scratch_bytes(n, frame_cap)))
-            bufs.append(scratch)
-            self.run_decode(L, None, n, verify, out, scratch, frame_cap, max_in, max_out)
-            # part_first u32 (n + 1), chunk_len u32 (n), flag u32
-            feed = DeviceBuffer(_a8(4 * (n + 1)) + _a8(4 * n) + 8)
-            bufs.append(feed)
-            part_first, chunk_len = feed.ptr, feed.ptr + _a8(4 * (n + 1))
-            flag = chunk_len + _a8(4 * n)
-            _lib.check(lib().kdb_hstable_dev_feed(None, L.p("out_len"), L.p("status"), L.p("dstatus"), n, part_first,
-                                                  chunk_len, flag), "kdb_hstable_dev_feed")
-            raw = max(out_bytes, 1)
-            pscratch_bytes = int(lib().kdb_put_scratch_bytes(n, n, raw))
-            pscratch = DeviceBuffer(pscratch_bytes)
-            bufs.append(pscratch)
-            entries = DeviceBuffer(raw + n * (72 + kmax) + (raw // 65536 + n + 1) * 16 + 64)
-            bufs.append(entries)
-            po = DeviceBuffer(n * 32 + 64)
-            bufs.append(po)
-            o = po.ptr
-            e_off, e_len, hashed, crc, kind, status, total = (o, o + 8 * n, o + 12 * n, o + 20 * n, o + 24 * n,
-                                                              o + 28 * n, o + 32 * n)
-            _lib.check(lib().kdb_put_entries_batch(
-                None, L.keys.ptr, L.p("key_off"), L.p("key_len"), out.ptr, L.p("out_off"), L.p("out_len"), part_first,
-                chunk_len, n, max_out, n, self.hash_type, pscratch.ptr, pscratch_bytes, raw, entries.ptr, e_off,
-                e_len, total, hashed, crc, kind, status), "kdb_put_entries_batch")
-            if int(feed.download(4, flag - feed.ptr, dtype=np.uint32)[0]):
-                self._compact_fail(L, n, True)
-            w.append_ptrs(None, entries.ptr, e_off, e_len, hashed, kind, status, n)
-            _lib.check(lib().kdb_lz4_stream_sync(None), "sync")     # the window's buffers are read by queued work
-        finally:
-            for b in bufs:
-                b.free()
-
-    def _compact_fail(self, L: _Lookup, n: int, decoded: bool) -> None:
-        """The error compacted() raises, for the window's first value that does not decode."""
-        status = L.meta.download(4 * n, L.off["status"], dtype=np.int32)
-        dstatus = L.meta.download(4 * n, L.off["dstatus"], dtype=np.int32) if decoded else status
-        koff = L.meta.download(8 * n, L.off["key_off"], dtype=np.uint64)
-        klen = L.meta.download(4 * n, L.off["key_len"], dtype=np.uint32)
-        for i in range(n):
-            s = int(status[i]) or int(dstatus[i])
-            if s:
-                key = L.keys.download(int(klen[i]), int(koff[i])).tobytes() if klen[i] else b""
-                raise _lib.HipError(f"compacted: value of {key!r} does not decode (status {s})")
-        raise _lib.HipError("compacted: a value of the window does not decode")
+    def snapshot(self) -> "HSTableSnapshot":
+        """A read-only view of the index as it is now (kdb_snapshot_create;
+        Database::NewSnapshot): its get, locate, scan, items and compaction go
+        on answering over the files held at this moment while refresh() /
+        add_files() add newer ones.  It copies nothing and costs no device
+        work.  Entries of the writer's still open file are in neither; close
+        or cut the file and refresh() first to have them in the snapshot.
+        close() it, or use it as a context manager; close() of the index
+        closes the snapshots still open."""
+        return HSTableSnapshot(self)
 
     def close(self) -> None:
+        for s in list(self._snapshots or ()):
+            s.close()
         if self.h:
             lib().kdb_index_destroy(self.h)
             self.h = None
         self.files.free()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HSTableSnapshot(_ReadPath):
+    """HSTableIndex.snapshot(): the index as of the moment it was taken
+    (include/kdb_snapshot.h).  `entries`, `names` and `file_status` are the
+    index's of that moment; locate, get, scan_prepare, scan_sort_steps, scan,
+    items, compacted and compacted_device are HSTableIndex's own, and answer
+    as an HSTableIndex made fresh over `names` alone.  Its prepared scan is
+    its own: adds to the index do not drop it.  Not to run concurrently with
+    calls on the index or its other snapshots."""
+
+    _ABI = "kdb_snapshot"
+
+    def __init__(self, index: HSTableIndex):
+        self.h = None
+        self._scan = None
+        self.index = index
+        self.hash_type = index.hash_type
+        self.names = list(index.names)
+        self.file_status = dict(index.file_status)
+        h = ctypes.c_void_p()
+        _lib.check(lib().kdb_snapshot_create(index.h, ctypes.byref(h)), "kdb_snapshot_create")
+        self.h = h.value
+        if index._snapshots is None:
+            index._snapshots = []
+        index._snapshots.append(self)
+        n, f = ctypes.c_uint64(0), ctypes.c_uint32(0)
+        _lib.check(lib().kdb_snapshot_entry_count(self.h, ctypes.byref(n)), "kdb_snapshot_entry_count")
+        _lib.check(lib().kdb_snapshot_file_count(self.h, ctypes.byref(f)), "kdb_snapshot_file_count")
+        self.entries = n.value
+        assert f.value == len(self.names)
+
+    @property
+    def files(self):
+        """The index's files buffer (the value decode reads it)."""
+        return self.index.files
+
+    def close(self) -> None:
+        if self.h:
+            lib().kdb_snapshot_release(self.h)
+            self.h = None
+            self.index._snapshots.remove(self)
+
+    def __enter__(self) -> "HSTableSnapshot":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
 
     def __del__(self):
         try:
