@@ -128,6 +128,18 @@ SIGNATURES = {
     "kdb_hstable_dev_download": (_i, [_vp, _u32, _vp, _vp]),
     "kdb_hstable_dev_reset": (_i, [_vp]),
     "kdb_hstable_dev_feed": (_i, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+    # include/kdb_compact.h (compaction by copy and the hand-over)
+    "kdb_compact_scratch_bytes": (_u64, [_u32]),
+    "kdb_compact_piece_bytes": (_u32, []),
+    "kdb_compact_plan_batch": (_i, [_vp, _vp, _u64] + [_vp] * 8 + [_u32, _u64, _u32, _vp, _u64] + [_vp] * 6),
+    "kdb_compact_entries_batch": (_i, [_vp, _vp, _u64, _vp, _u64] + [_vp] * 8 + [_u32, _u32, _vp, _u64, _vp, _u64]
+                                  + [_vp] * 6 + [_c.POINTER(_u32)]),
+    "kdb_compact_entries_batch_timed": (_i, [_vp, _vp, _u64, _vp, _u64] + [_vp] * 8 + [_u32, _u32, _vp, _u64, _vp,
+                                             _u64] + [_vp] * 6 + [_c.POINTER(_u32), _c.POINTER(_c.c_float)]),
+    "kdb_index_view_timestamp": (_i, [_vp, _u32, _c.POINTER(_u64)]),
+    "kdb_hstable_dev_create2": (_i, [_u64, _u32, _u64, _u32, _u64, _c.POINTER(_vp)]),
+    "kdb_hstable_dev_open_bytes": (_i, [_vp, _c.POINTER(_u64)]),
+    "kdb_hstable_dev_adopt": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32]),
     # include/kdb_recover.h (files without a usable footer, recovered in device memory)
     "kdb_hstable_recover_bound": (_u64, [_u64]),
     "kdb_hstable_recover_scratch_bytes": (_u64, [_vp, _u32]),

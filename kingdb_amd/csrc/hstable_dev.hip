@@ -282,7 +282,7 @@ __global__ __launch_bounds__(kCloseBlock) void hsd_crc_kernel(const uint8_t* __r
 __global__ __launch_bounds__(64) void hsd_close_kernel(uint8_t* __restrict__ arena, uint64_t arena_bytes,
                                                        const cut::FileRec* __restrict__ recs,
                                                        const Place* __restrict__ places,
-                                                       const uint32_t* __restrict__ piece_crc) {
+                                                       const uint32_t* __restrict__ piece_crc, uint32_t filetype) {
   __shared__ uint32_t s_t[256];
   const uint32_t r = blockIdx.x;
   const cut::FileRec f = recs[r];
@@ -293,8 +293,8 @@ __global__ __launch_bounds__(64) void hsd_close_kernel(uint8_t* __restrict__ are
   crc::stage_table(s_t);
   __syncthreads();
   if (threadIdx.x != 0) return;
-  // filetype kUncompactedRegularType; the rows begin where the entries end
-  hsc::close_file(arena + rows, nbytes, piece_crc + (uint64_t)r * hsc::kCrcPieces, 1u,
+  // the rows begin where the entries end
+  hsc::close_file(arena + rows, nbytes, piece_crc + (uint64_t)r * hsc::kCrcPieces, filetype,
                   (f.flags & cut::kPadding) ? 1u : 0u, f.fs_end, pl.nrows_total, s_t);
 }
 
@@ -354,6 +354,11 @@ struct kdb_hstable_dev {
   uint64_t staged = 0;                    // and their bytes, staged at the arena's end
   uint64_t next_off = 0;                  // the end of the last closed file
   uint32_t fileid = 0;
+  // kdb_hstable_dev_create2 (kdb_compact.h): the type of the files written and,
+  // where nonzero, the timestamp every header carries instead of the file's id
+  // (LockSequenceTimestamp).  kdb_hstable_dev_adopt returns both to 1 and 0.
+  uint32_t filetype = 1;                  // kUncompactedRegularType
+  uint64_t ts_lock = 0;
   std::vector<uint64_t> file_off, file_size;
   std::vector<uint32_t> file_id;
 };
@@ -416,7 +421,7 @@ void file_header(const kdb_hstable_dev* w, uint64_t timestamp, uint8_t* b) {
   memset(b, 0, 72);
   put32(b + 4, 1);                        // data format 1.0 (format.h:28-29)
   put32(b + 8, 0);
-  put32(b + 12, 1);                       // kUncompactedRegularType
+  put32(b + 12, w->filetype);
   put64(b + 16, timestamp);
   put32(b, host_crc32c(b + 4, 20));
   memcpy(b + 24, w->opts, 48);
@@ -453,7 +458,7 @@ bool place_records(const kdb_hstable_dev* w, const cut::FileRec* recs, uint32_t 
       p.open_rows = 0;
       p.staged = 0;
       p.fileid++;
-      file_header(w, p.fileid, pl.hdr);     // timestamps count with the ids
+      file_header(w, w->ts_lock ? w->ts_lock : p.fileid, pl.hdr);     // timestamps count with the ids, unless locked
     } else if (r != 0 || !p.st.open || f.fs != p.st.fsize) {
       return false;                         // only the first record continues a file
     }
@@ -541,7 +546,7 @@ hipError_t write_files(kdb_hstable_dev* w, hipStream_t st, const Work& k, const 
                        k.recs, k.places, k.piece_crc);
     KDB_TRY(hipGetLastError());
     hipLaunchKernelGGL(hsd_close_kernel, dim3(nrec), dim3(64), 0, st, w->arena, w->arena_bytes, k.recs, k.places,
-                       k.piece_crc);
+                       k.piece_crc, w->filetype);
   }
   return hipGetLastError();
 }
@@ -648,7 +653,12 @@ extern "C" uint64_t kdb_hstable_dev_arena_bytes(uint64_t hstable_size, uint64_t 
 
 extern "C" int kdb_hstable_dev_create(uint64_t hstable_size, uint32_t hash_type, uint64_t arena_bytes,
                                       kdb_hstable_dev** w) {
-  if (!w || hash_type > 1 || hstable_size <= cut::kHeaderBlock || arena_bytes < cut::kHeaderBlock + 64u ||
+  return kdb_hstable_dev_create2(hstable_size, hash_type, arena_bytes, 1u, 0u, w);
+}
+
+extern "C" int kdb_hstable_dev_create2(uint64_t hstable_size, uint32_t hash_type, uint64_t arena_bytes,
+                                       uint32_t filetype, uint64_t timestamp_lock, kdb_hstable_dev** w) {
+  if (!w || hash_type > 1 || (filetype != 1u && filetype != 2u) || hstable_size <= cut::kHeaderBlock || arena_bytes < cut::kHeaderBlock + 64u ||
       arena_bytes > (1ull << 46))
     return KDB_PUT_EINVAL;
   int count = 0;
@@ -660,6 +670,8 @@ extern "C" int kdb_hstable_dev_create(uint64_t hstable_size, uint32_t hash_type,
   p->sb = hstable_size;
   p->hash_type = hash_type;
   p->arena_bytes = arena_bytes;
+  p->filetype = filetype;
+  p->ts_lock = timestamp_lock;
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->arena), arena_bytes);
   if (e == hipSuccess)
     e = hipHostMalloc(reinterpret_cast<void**>(&p->pinned), sizeof(PlanHead) + kHeadRecs * sizeof(cut::FileRec),
@@ -748,6 +760,60 @@ extern "C" int kdb_hstable_dev_reset(kdb_hstable_dev* w) {
   w->file_off.clear();
   w->file_size.clear();
   w->file_id.clear();
+  return KDB_PUT_OK;
+}
+
+extern "C" int kdb_hstable_dev_open_bytes(const kdb_hstable_dev* w, uint64_t* bytes) {
+  if (!w || !bytes) return KDB_PUT_EINVAL;
+  *bytes = w->st.open ? w->st.fsize : 0u;
+  return KDB_PUT_OK;
+}
+
+// Compaction() steps 8, 9 and 14 (storage_engine.h:940-1010): the compacted
+// files take ids above every id in use, and the files the compaction did not
+// cover stay in the database beside them -- here, in this writer's arena.
+extern "C" int kdb_hstable_dev_adopt(kdb_hstable_dev* w, void* stream, uint32_t first_fileid, const uint8_t* d_src,
+                                     const uint64_t* src_off, const uint64_t* src_size, const uint32_t* src_id,
+                                     uint32_t nsrc) {
+  if (!w || first_fileid == 0 || (nsrc && (!d_src || !src_off || !src_size || !src_id))) return KDB_PUT_EINVAL;
+  if (w->st.open) return KDB_PUT_EINVAL;
+  const uint64_t own = w->file_id.size();
+  if ((uint64_t)first_fileid + own + 1u > 0xFFFFFFFFull) return KDB_PUT_EINVAL;
+  std::vector<uint32_t> ids(src_id, src_id + nsrc);
+  std::sort(ids.begin(), ids.end());
+  for (uint32_t f = 0; f < nsrc; f++)
+    if (ids[f] == 0 || ids[f] >= first_fileid || (f && ids[f] == ids[f - 1u])) return KDB_PUT_EINVAL;
+  // where the adopted files go: nothing is staged while no file is open, so
+  // the room ends with the arena
+  std::vector<uint64_t> at(nsrc);
+  uint64_t pos = w->next_off;
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(w->arena), a1 = a0 + w->arena_bytes;
+  for (uint32_t f = 0; f < nsrc; f++) {
+    if (src_size[f] > hs::kMaxFileSize || src_off[f] > (1ull << 46)) return KDB_PUT_EINVAL;
+    pos = align64(pos);
+    if (pos > w->arena_bytes || src_size[f] > w->arena_bytes - pos) return KDB_PUT_EINVAL;
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src) + src_off[f], s1 = s0 + src_size[f];
+    if (s0 < a1 && a0 < s1) return KDB_PUT_EINVAL;
+    at[f] = pos;
+    pos += src_size[f];
+  }
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = st != w->last ? hipStreamSynchronize(w->last) : hipSuccess;
+  for (uint32_t f = 0; f < nsrc && e == hipSuccess; f++)
+    if (src_size[f])
+      e = hipMemcpyAsync(w->arena + at[f], d_src + src_off[f], src_size[f], hipMemcpyDeviceToDevice, st);
+  if (e != hipSuccess) return hip_code(e);   // bytes behind next_off are nobody's: the writer is as before
+  w->last = st;
+  for (uint64_t i = 0; i < own; i++) w->file_id[i] = first_fileid + (uint32_t)i;
+  for (uint32_t f = 0; f < nsrc; f++) {
+    w->file_off.push_back(at[f]);
+    w->file_size.push_back(src_size[f]);
+    w->file_id.push_back(src_id[f]);
+  }
+  w->next_off = pos;
+  w->fileid = first_fileid + (uint32_t)own - 1u;      // above the adopted ids too: they are below first_fileid
+  w->filetype = 1u;
+  w->ts_lock = 0u;
   return KDB_PUT_OK;
 }
 

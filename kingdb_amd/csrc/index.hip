@@ -89,6 +89,7 @@ struct FileRec {
   uint64_t num_entries, offset_indexes, timestamp;
   uint32_t flags;
   int32_t status;
+  uint32_t filetype, pad;        // the header's (kdb_index_view_timestamp refuses the large type)
 };
 
 struct ParseFile {
@@ -124,7 +125,7 @@ __global__ __launch_bounds__(kFileBlock) void index_file_kernel(const uint8_t* _
   const uint8_t* p = files + file_off[f];
   const uint64_t size = file_size[f];
   if (threadIdx.x == 0) {
-    FileRec r{0, 0, 0, 0, 0};
+    FileRec r{0, 0, 0, 0, 0, 0, 0};
     hs::FileHeader fh;
     hs::Footer ft;
     uint32_t want = 0;
@@ -141,6 +142,7 @@ __global__ __launch_bounds__(kFileBlock) void index_file_kernel(const uint8_t* _
         r.num_entries = ft.num_entries;
         r.offset_indexes = ft.offset_indexes;
         r.timestamp = fh.timestamp;
+        r.filetype = fh.filetype;
         r.flags = ft.flags;
         want = ft.crc32;
       }
@@ -730,6 +732,7 @@ struct kdb_index {
   // have room for (they grow geometrically)
   std::vector<uint64_t> file_off, file_size, timestamp;
   std::vector<int32_t> status;
+  std::vector<uint32_t> filetype;        // the headers' file types, per slot
   std::vector<uint32_t> rank, rank_file;
   uint32_t nloaded = 0;                  // files of status 0: the ranks in use
   uint64_t row_cap = 0;
@@ -788,6 +791,7 @@ void index_release(kdb_index* ix) {
   ix->file_off.clear();
   ix->file_size.clear();
   ix->timestamp.clear();
+  ix->filetype.clear();
   ix->status.clear();
   ix->rank.clear();
   ix->rank_file.clear();
@@ -862,6 +866,7 @@ hipError_t index_add(kdb_index* ix, hipStream_t st, const uint64_t* file_off, co
   std::vector<uint64_t> h_off(ix->file_off), h_size(ix->file_size), h_ts(ix->timestamp);
   std::vector<uint32_t> h_id(ix->fileid), rank(ix->rank), rank_file(ix->rank_file);
   std::vector<int32_t> h_status(ix->status);
+  std::vector<uint32_t> h_type(ix->filetype);
   std::vector<FileRec> rec(nadd);
   std::vector<int32_t> status(nadd);
   std::vector<uint32_t> order, tile_file, bad(nf);
@@ -1010,6 +1015,7 @@ hipError_t index_add(kdb_index* ix, hipStream_t st, const uint64_t* file_off, co
   }
   for (uint32_t f = 0; f < nadd; f++) {
     h_ts.push_back(rec[f].timestamp);
+    h_type.push_back(rec[f].filetype);
     h_status.push_back(status[f]);
   }
   KDB_TRY(hipStreamSynchronize(st));
@@ -1034,6 +1040,7 @@ hipError_t index_add(kdb_index* ix, hipStream_t st, const uint64_t* file_off, co
   ix->file_size.swap(h_size);
   ix->fileid.swap(h_id);
   ix->timestamp.swap(h_ts);
+  ix->filetype.swap(h_type);
   ix->status.swap(h_status);
   ix->rank.swap(rank);
   ix->rank_file.swap(rank_file);
@@ -1119,6 +1126,19 @@ extern "C" int kdb_index_add_stats(const kdb_index* ix, uint32_t* merged, uint64
   if (merged) *merged = 0u;                // the buckets are always rebuilt
   if (nbuckets) *nbuckets = ix->nbuckets;
   if (rows_parsed) *rows_parsed = ix->add_rows_parsed;
+  return KDB_PUT_OK;
+}
+
+// kdb_compact.h: the timestamp the compacted files lock (storage_engine.h:806-810, 927-934)
+extern "C" int kdb_index_view_timestamp(const kdb_index* ix, uint32_t nfiles, uint64_t* timestamp_max) {
+  if (!ix || !timestamp_max || nfiles > ix->nfiles) return KDB_PUT_EINVAL;
+  uint64_t ts = 0;
+  for (uint32_t f = 0; f < nfiles; f++) {
+    if (ix->status[f] != 0) continue;
+    if (ix->filetype[f] & 4u) return KDB_PUT_EINVAL;     // kCompactedLargeType
+    ts = std::max(ts, ix->timestamp[f]);
+  }
+  *timestamp_max = ts;
   return KDB_PUT_OK;
 }
 

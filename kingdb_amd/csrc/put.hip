@@ -46,6 +46,7 @@
 #include "../../include/kdb_lz4.h"
 #include "../../include/kdb_ops.h"
 #include "crc_device.h"
+#include "entry_encode.h"
 #include "hash_device.h"
 #include "lz4_device.h"
 
@@ -60,40 +61,10 @@ namespace {
 
 constexpr uint32_t kTypeDelete = 0x1, kEntryFull = 0x8, kUncompacted = 0x2, kHasPadding = 0x4;   // format.h:34-42
 
-// ----------------------------------------------------------------- CRC-8 of the header
-// crc32c::crc8 (crc32c.cc:439-475): reflected, polynomial 0xB2, pre/post xor 0xff.
-struct Crc8Table {
-  uint8_t t[256];
-};
-constexpr Crc8Table make_crc8() {
-  Crc8Table c{};
-  for (unsigned i = 0; i < 256; i++) {
-    unsigned v = i;
-    for (int k = 0; k < 8; k++) v = (v & 1u) ? (v >> 1) ^ 0xB2u : v >> 1;
-    c.t[i] = (uint8_t)v;
-  }
-  return c;
-}
-__constant__ Crc8Table kCrc8 = make_crc8();
-
-__host__ __device__ __forceinline__ uint32_t varint_len(uint64_t v) {
-  uint32_t n = 1;
-  while (v >= 128) { v >>= 7; n++; }
-  return n;
-}
-__device__ __forceinline__ uint8_t* put_varint(uint8_t* p, uint64_t v) {
-  while (v >= 128) { *p++ = (uint8_t)(v | 128); v >>= 7; }
-  *p++ = (uint8_t)v;
-  return p;
-}
+// (the CRC-8 table, the varints, header_len and the header encoder: entry_encode.h)
 
 __host__ __device__ __forceinline__ uint64_t padding_size(uint64_t size_value) {   // format.h:63-71
   return (size_value / 65536u + 1u) * 8u;
-}
-// EntryHeader::EncodeTo's size (compression on: fixed64 size_value_compressed).
-__host__ __device__ __forceinline__ uint32_t header_len(uint32_t flags, uint64_t klen, uint64_t size_value,
-                                                        uint64_t pad) {
-  return 1u + 4u + varint_len(flags) + varint_len(klen) + varint_len(size_value) + 8u + varint_len(pad) + 8u;
 }
 
 // Part modes (how chunk_final is made from the chunk), plus a flag for chunks
@@ -474,18 +445,7 @@ __global__ __launch_bounds__(kEntryBlock) void put_entry_kernel(
       const uint64_t hh = del && !delete_hashed ? 0u : h;
       hashed[v] = h;
       crc_out[v] = crc;
-      uint8_t* q = hdr + 1;
-      const uint32_t cc = L.hdr_crc_final ? crc : 0u;
-      for (int i = 0; i < 4; i++) *q++ = (uint8_t)(cc >> (8 * i));
-      q = put_varint(q, L.flags);
-      q = put_varint(q, klen);
-      q = put_varint(q, V);
-      for (int i = 0; i < 8; i++) *q++ = (uint8_t)(L.svc_hdr >> (8 * i));
-      q = put_varint(q, L.pad_hdr);
-      for (int i = 0; i < 8; i++) *q++ = (uint8_t)(hh >> (8 * i));
-      uint32_t c8 = 0xffu;                        // crc8(0, header + 1, hl - 1)
-      for (uint32_t i = 1; i < hl; i++) c8 = s_c8[(c8 ^ hdr[i]) & 0xffu];
-      hdr[0] = (uint8_t)(c8 ^ 0xffu);
+      encode_entry_header(hdr, hl, L.hdr_crc_final ? crc : 0u, L.flags, klen, V, L.svc_hdr, L.pad_hdr, hh, s_c8);
     }
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");

@@ -13,6 +13,12 @@ set of closed HSTable files and the batched lookup in front of the decoder.
   .items(batch)           a generator over all of them, window by window
   .compacted(size)        the live entries written again as a fresh database
   .compacted_device(size) the same with no value byte leaving device memory
+  .compact_copy(size)     the reference's compaction: the live entries copied
+                          as they are stored, no decode, into type-2 files
+                          with the view's largest timestamp (kdb_compact.h)
+  .compact(snapshot)      compact_copy of a snapshot plus the hand-over:
+                          (writer, index) over the compacted files and the
+                          files added since (StorageEngine::Compaction)
   HSTableIndex.from_resident(writer)
                           an index over the files a put.DeviceHSTableWriter
                           holds in device memory, with no upload
@@ -392,6 +398,85 @@ class _ReadPath:
             for b in bufs:
                 b.free()
 
+    def compact_copy(self, hstable_size: int = 32 << 20, batch: int = 65536, spare_bytes: int = 0,
+                     filetype: int = 2, lock: bool = True):
+        """The compaction of the reference (StorageEngine::Compaction, steps
+        6-7): every live entry of the view copied as it is stored -- a fresh
+        header, the key, the stored value bytes, no decode -- into files of
+        type kCompactedRegularType that all carry the largest timestamp of the
+        view's files.  Returns the closed put.DeviceHSTableWriter (ids from 1
+        until HSTableIndex.compact() hands it over), its arena sized for the
+        copy plus `spare_bytes`.  Each scan window goes scan ->
+        kdb_compact_entries_batch -> the writer; no value byte reaches the
+        host, which per window sees the plan's total and the writer's plan.
+        The window buffers are allocated once, for the largest window.
+        filetype=1, lock=False writes the same windows as files of an ordinary
+        database, timestamps counting with the ids: byte for byte the files of
+        compacted_device() where every live entry is self-contained."""
+        from . import put
+        batch = max(batch, 1)
+        live, _, kmax = self._prepared(0, None)
+        windows = [(first, min(batch, live - first)) for first in range(0, live, batch)]
+        big = 1 << 62
+        ts = ctypes.c_uint64(0)
+        ih, nfiles = self._view()
+        _lib.check(lib().kdb_index_view_timestamp(ih, nfiles, ctypes.byref(ts)), "kdb_index_view_timestamp")
+        nmax = max([n for _, n in windows], default=1)
+        L = _Lookup(nmax, nmax * kmax)
+        bufs = [L]
+        w = None
+        try:
+            scratch_bytes = int(lib().kdb_compact_scratch_bytes(nmax))
+            scratch = DeviceBuffer(scratch_bytes)
+            bufs.append(scratch)
+            po = DeviceBuffer(nmax * 32 + 64)      # entry_off u64, hashed u64, entry_len, kind, status u32, total u64
+            bufs.append(po)
+            o = po.ptr
+            e_off, hashed, e_len, kind, status, total = (o, o + 8 * nmax, o + 16 * nmax, o + 20 * nmax, o + 24 * nmax,
+                                                         o + _a8(28 * nmax))
+
+            def args(n):
+                return (L.keys.ptr, L.keys.nbytes, L.p("key_off"), L.p("key_len"), L.p("stored_off"), L.p("avail"),
+                        L.p("svc"), L.p("size"), L.p("checksum"), L.p("status"), n)
+
+            # sizing pass: plans only, 8 bytes per window come down
+            bound = most = 0
+            for first, n in windows:
+                self.run_scan(L, None, first, n, big)
+                _lib.check(lib().kdb_compact_plan_batch(None, *args(n), self.files.nbytes, self.hash_type, scratch.ptr,
+                                                        scratch_bytes, e_off, e_len, total, hashed, kind, status),
+                           "kdb_compact_plan_batch")
+                t = int(po.download(8, total - o, dtype=np.uint64)[0])
+                bound += t
+                most = max(most, t)
+            w = put.DeviceHSTableWriter(hstable_size, self.hash_type,
+                                        put.DeviceHSTableWriter.arena_bytes(hstable_size, bound, live) + spare_bytes,
+                                        filetype=filetype, timestamp_lock=ts.value if lock else 0)
+            entries = DeviceBuffer(most + 64)
+            bufs.append(entries)
+            refused = ctypes.c_uint32(0)
+            for first, n in windows:
+                self.run_scan(L, None, first, n, big)
+                _lib.check(lib().kdb_compact_entries_batch(
+                    None, self.files.ptr, self.files.nbytes, *args(n), self.hash_type, scratch.ptr, scratch_bytes,
+                    entries.ptr, most, e_off, e_len, total, hashed, kind, status, ctypes.byref(refused)),
+                    "kdb_compact_entries_batch")
+                if refused.value:
+                    raise _lib.HipError(f"compact_copy: {refused.value} entries of window {first} have a stored "
+                                        "length their file does not hold")
+                # the next window's work is queued behind this append on the same stream
+                w.append_ptrs(None, entries.ptr, e_off, e_len, hashed, kind, status, n)
+            w.close()
+            _lib.check(lib().kdb_lz4_stream_sync(None), "sync")     # the buffers are read by queued work
+        except Exception:
+            if w is not None:
+                w.free()                    # waits for the writer's queued work
+            raise
+        finally:
+            for b in bufs:
+                b.free()
+        return w
+
     def _compact_fail(self, L: _Lookup, n: int, decoded: bool) -> None:
         """The error compacted() raises, for the window's first value that does not decode."""
         status = L.meta.download(4 * n, L.off["status"], dtype=np.int32)
@@ -611,6 +696,46 @@ class HSTableIndex(_ReadPath):
         _lib.check(lib().kdb_index_pairs(self.h, h.ctypes.data, loc.ctypes.data), "kdb_index_pairs")
         return h[:self.entries], loc[:self.entries]
 
+    def _view(self) -> tuple[int, int]:
+        """(index handle, file slots of the view), for kdb_index_view_timestamp."""
+        return self.h, len(self.names)
+
+    def compact(self, snapshot: "HSTableSnapshot | None" = None, hstable_size: int = 32 << 20, batch: int = 65536,
+                spare_bytes: int = 0):
+        """The compaction of a snapshot (one is taken if none is given) and
+        the hand-over, StorageEngine::Compaction as a whole: returns (writer,
+        index).  The writer holds the snapshot's live entries in compacted
+        files (compact_copy), numbered above every id this index holds, and
+        behind them, copied as they are, every file of this index that is not
+        a loaded file of the snapshot: the files added since, and files that
+        loaded with a nonzero status.  `index` is
+        HSTableIndex.from_resident(writer); puts appended to the writer and
+        refresh()ed into it go on as on any writer, `spare_bytes` being the
+        arena's room for them.  This index, its writer and its arena are left
+        untouched: closing and freeing them is where the memory of the
+        overwritten and deleted entries is reclaimed.  ValueError where this
+        index's writer has a file open: close or cut it and refresh() first."""
+        if self._owner is not None and self._owner.open_bytes():
+            raise ValueError("compact: the writer has an open file; close or cut it and refresh() first")
+        if snapshot is not None and snapshot.index is not self:
+            raise ValueError("compact: the snapshot is of another index")
+        snap = snapshot if snapshot is not None else self.snapshot()
+        try:
+            loaded = {f for f in snap.names if snap.file_status[f] == 0}
+            rest = [i for i, f in enumerate(self.names) if f not in loaded]
+            need = sum((int(self.file_size[i]) + 63) & ~63 for i in rest) + 64
+            w = snap.compact_copy(hstable_size, batch, spare_bytes + need)
+        finally:
+            if snapshot is None:
+                snap.close()
+        try:
+            first = max((int(f) for f in self.fileid), default=0) + 1
+            w.adopt(first, self.files.ptr, self.file_off[rest], self.file_size[rest], self.fileid[rest])
+            return w, HSTableIndex.from_resident(w)
+        except Exception:
+            w.free()
+            raise
+
     def snapshot(self) -> "HSTableSnapshot":
         """A read-only view of the index as it is now (kdb_snapshot_create;
         Database::NewSnapshot): its get, locate, scan, items and compaction go
@@ -671,6 +796,9 @@ class HSTableSnapshot(_ReadPath):
     def files(self):
         """The index's files buffer (the value decode reads it)."""
         return self.index.files
+
+    def _view(self) -> tuple[int, int]:
+        return self.index.h, len(self.names)
 
     def close(self) -> None:
         if self.h:

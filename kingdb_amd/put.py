@@ -341,12 +341,20 @@ class DeviceHSTableWriter:
     entries in 2 Mi puts).  An append that does not fit raises HipError and
     leaves the writer as it was."""
 
-    def __init__(self, hstable_size: int = 32 << 20, hash_type: int = 1, arena_bytes: int | None = None):
+    def __init__(self, hstable_size: int = 32 << 20, hash_type: int = 1, arena_bytes: int | None = None,
+                 filetype: int = 1, timestamp_lock: int = 0):
+        """`filetype` 2 and `timestamp_lock` make the files of a compaction
+        (kdb_hstable_dev_create2): kCompactedRegularType, every header with
+        the locked timestamp; adopt() returns the writer to type 1."""
         if arena_bytes is None:
             arena_bytes = self.arena_bytes(hstable_size, 256 << 20, 2 << 20)
         h = ctypes.c_void_p()
-        _lib.check(lib().kdb_hstable_dev_create(hstable_size, hash_type, arena_bytes, ctypes.byref(h)),
-                   "hstable_dev_create")
+        if filetype == 1 and timestamp_lock == 0:
+            _lib.check(lib().kdb_hstable_dev_create(hstable_size, hash_type, arena_bytes, ctypes.byref(h)),
+                       "hstable_dev_create")
+        else:
+            _lib.check(lib().kdb_hstable_dev_create2(hstable_size, hash_type, arena_bytes, filetype, timestamp_lock,
+                                                     ctypes.byref(h)), "hstable_dev_create2")
         self.h = h.value
         self.hstable_size, self.hash_type, self.arena = hstable_size, hash_type, arena_bytes
 
@@ -368,6 +376,27 @@ class DeviceHSTableWriter:
 
     def close(self) -> None:
         _lib.check(lib().kdb_hstable_dev_close(self.h), "hstable_dev_close")
+
+    def open_bytes(self) -> int:
+        """The size so far of the file that is open, 0 where none is."""
+        b = ctypes.c_uint64(0)
+        _lib.check(lib().kdb_hstable_dev_open_bytes(self.h, ctypes.byref(b)), "hstable_dev_open_bytes")
+        return b.value
+
+    def adopt(self, first_fileid: int, src_ptr: int, off, size, fileid, stream: Stream | None = None) -> None:
+        """The hand-over of a compaction (kdb_hstable_dev_adopt): the writer's
+        own closed files become first_fileid, first_fileid + 1, ...; the files
+        src_ptr[off[f] .. +size[f]) are copied, device to device, behind them
+        with their ids; files opened afterwards are ordinary ones.  Refused
+        (HipError EINVAL, the writer as before): an open file, an id
+        >= first_fileid or given twice, bytes that do not fit the arena."""
+        off, size, fileid = (np.ascontiguousarray(off, np.uint64), np.ascontiguousarray(size, np.uint64),
+                             np.ascontiguousarray(fileid, np.uint32))
+        n = len(fileid)
+        _lib.check(lib().kdb_hstable_dev_adopt(self.h, stream.ptr if stream else None, first_fileid,
+                                               src_ptr if n else None, off.ctypes.data if n else None,
+                                               size.ctypes.data if n else None, fileid.ctypes.data if n else None, n),
+                   "hstable_dev_adopt")
 
     def reset(self) -> None:
         """A fresh directory; the arena is kept."""
