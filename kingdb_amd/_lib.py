@@ -27,6 +27,14 @@ _i = _c.c_int
 _u32 = _c.c_uint32
 _u64 = _c.c_uint64
 
+
+
+class OpenFile(ctypes.Structure):
+    """struct kdb_open_file (include/kdb_index_tail.h)."""
+    _fields_ = [("open", _u32), ("fileid", _u32), ("incomplete", _u32), ("pad", _u32), ("timestamp", _u64),
+                ("file_off", _u64), ("bytes", _u64), ("rows", _u64), ("row_bytes", _u64), ("rows_last", _u64)]
+
+
 # name -> (restype, argtypes); mirrors include/kdb_lz4.h one for one.
 SIGNATURES = {
     "kdb_lz4_version": (_i, []),
@@ -140,6 +148,12 @@ SIGNATURES = {
     "kdb_hstable_dev_create2": (_i, [_u64, _u32, _u64, _u32, _u64, _c.POINTER(_vp)]),
     "kdb_hstable_dev_open_bytes": (_i, [_vp, _c.POINTER(_u64)]),
     "kdb_hstable_dev_adopt": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32]),
+    # include/kdb_index_tail.h (the writer's open file read through the index)
+    "kdb_hstable_dev_open_file": (_i, [_vp, _c.POINTER(OpenFile)]),
+    "kdb_index_set_tail": (_i, [_vp, _vp, _vp, _c.POINTER(OpenFile), _u32, _c.POINTER(_u64)]),
+    "kdb_index_drop_tail": (_i, [_vp, _vp]),
+    "kdb_index_tail_stats": (_i, [_vp, _c.POINTER(_u32), _c.POINTER(_u32), _c.POINTER(_u64), _c.POINTER(_u64),
+                                  _c.POINTER(_u64), _c.POINTER(_u64)]),
     # include/kdb_recover.h (files without a usable footer, recovered in device memory)
     "kdb_hstable_recover_bound": (_u64, [_u64]),
     "kdb_hstable_recover_scratch_bytes": (_u64, [_vp, _u32]),

@@ -740,6 +740,25 @@ extern "C" int kdb_hstable_dev_files(const kdb_hstable_dev* w, const uint8_t** d
   return KDB_PUT_OK;
 }
 
+// kdb_index_tail.h: the open file as kdb_index_set_tail reads it
+extern "C" int kdb_hstable_dev_open_file(const kdb_hstable_dev* w, kdb_open_file* out) {
+  if (!w || !out) return KDB_PUT_EINVAL;
+  const hipError_t e = hipStreamSynchronize(w->last);
+  if (e != hipSuccess) return hip_code(e);
+  *out = kdb_open_file{};
+  if (!w->st.open) return KDB_PUT_OK;
+  out->open = 1u;
+  out->fileid = w->fileid;
+  out->incomplete = w->st.incomplete ? 1u : 0u;
+  out->timestamp = w->ts_lock ? w->ts_lock : w->fileid;
+  out->file_off = w->open_base;
+  out->bytes = w->st.fsize;
+  out->rows = w->open_rows;
+  out->row_bytes = w->staged;
+  out->rows_last = w->arena_bytes - 1u;
+  return KDB_PUT_OK;
+}
+
 extern "C" int kdb_hstable_dev_download(const kdb_hstable_dev* w, uint32_t i, uint8_t* host_dst, void* stream) {
   if (!w || i >= w->file_id.size() || !host_dst) return KDB_PUT_EINVAL;
   hipStream_t st = (hipStream_t)stream;

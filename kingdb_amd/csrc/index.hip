@@ -31,6 +31,12 @@
 // storage/storage_engine.h:298-372; synchronous; the load is an add to an
 // empty handle): the kernels above over the new files alone, their rows
 // appended to the row arrays, then hist / scan / fill over all resident rows
+// Tail (include/kdb_index_tail.h; the rest of ProcessingLoopIndex: the file
+// still being written): the rows the device writer stages backwards at its
+// arena's end while a file is open, parsed by index_count_kernel<true> /
+// index_parse_kernel<true> (csrc/index_rows.h) behind the closed files' rows,
+// only the bytes staged since the last call; the open file takes the next file
+// slot and rank, and hist / scan / fill run over all resident rows
 // Lookup (stream-ordered):
 //   index_get_kernel     wave per key: hash, bucket scan, candidates in
 //                        descending sequence number, header decode + checks
@@ -70,9 +76,11 @@
 #include "hash_device.h"
 #include "hip_host.h"
 #include "hstable_decode.h"
+#include "index_rows.h"
 #include "lz4_device.h"
 
 namespace hs = kdb_hstable;
+namespace ir = kdb_index_rows;
 
 namespace kdb_lz4 {
 namespace {
@@ -168,13 +176,19 @@ __global__ __launch_bounds__(kFileBlock) void index_file_kernel(const uint8_t* _
 }
 
 // Terminators of the tile and, per thread, whether its byte is one.
+// kReversed (the tail, include/kdb_index_tail.h): the region is a range of the
+// device writer's staging, its byte p at files[reg_off - p]; reads stay inside
+// [reg_off - reg_len + 1, reg_off].  The `false` forms of the three functions
+// are the ones the load and the add have always run.
+template <bool kReversed>
 __device__ __forceinline__ bool tile_byte(const uint8_t* __restrict__ files, const ParseFile& F, uint32_t t,
                                           uint64_t* pos_out) {
   const uint64_t pos = (uint64_t)(t - F.first_tile) * kParseTile + threadIdx.x;
   *pos_out = pos;
-  return pos < F.reg_len && (files[F.reg_off + pos] & 0x80u) == 0;
+  return pos < F.reg_len && (files[kReversed ? F.reg_off - pos : F.reg_off + pos] & 0x80u) == 0;
 }
 
+template <bool kReversed>
 __global__ __launch_bounds__(kParseTile) void index_count_kernel(const uint8_t* __restrict__ files,
                                                                  const ParseFile* __restrict__ pf,
                                                                  const uint32_t* __restrict__ tile_file,
@@ -183,7 +197,7 @@ __global__ __launch_bounds__(kParseTile) void index_count_kernel(const uint8_t* 
   const uint32_t t = blockIdx.x;
   const ParseFile F = pf[tile_file[t]];
   uint64_t pos;
-  const bool term = tile_byte(files, F, t, &pos);
+  const bool term = tile_byte<kReversed>(files, F, t, &pos);
   const uint64_t m = ballot(term);
   if (lane_id() == 0) s_w[threadIdx.x / 64u] = (uint32_t)__popcll(m);
   __syncthreads();
@@ -194,6 +208,7 @@ __global__ __launch_bounds__(kParseTile) void index_count_kernel(const uint8_t* 
   }
 }
 
+template <bool kReversed>
 __global__ __launch_bounds__(kParseTile) void index_parse_kernel(
     const uint8_t* __restrict__ files, const ParseFile* __restrict__ pf, const uint32_t* __restrict__ tile_file,
     const uint64_t* __restrict__ tile_prefix, uint64_t* __restrict__ row_hash, uint32_t* __restrict__ row_off,
@@ -202,7 +217,7 @@ __global__ __launch_bounds__(kParseTile) void index_parse_kernel(
   const uint32_t t = blockIdx.x;
   const ParseFile F = pf[tile_file[t]];
   uint64_t pos;
-  const bool term = tile_byte(files, F, t, &pos);
+  const bool term = tile_byte<kReversed>(files, F, t, &pos);
   const uint64_t m = ballot(term);
   const uint32_t w = threadIdx.x / 64u;
   if (lane_id() == 0) s_w[w] = (uint32_t)__popcll(m);
@@ -213,26 +228,29 @@ __global__ __launch_bounds__(kParseTile) void index_parse_kernel(
     if (i < w) k += s_w[i];
     tile_total += s_w[i];
   }
-  if (threadIdx.x == 0 && t == F.first_tile + F.ntiles - 1u &&
-      tile_prefix[t] - tile_prefix[F.first_tile] + tile_total < F.nvar)
-    malformed[F.slot] = 1u;                                  // fewer varints than 2 * num_entries
+  if (kReversed) {
+    // a staging range holds exactly its rows: 2 * rows varints, the last byte ending one
+    if (threadIdx.x == 0 && t == F.first_tile + F.ntiles - 1u &&
+        tile_prefix[t] - tile_prefix[F.first_tile] + tile_total != F.nvar)
+      malformed[F.slot] = 1u;
+    if (pos == F.reg_len - 1u && !term) malformed[F.slot] = 1u;
+  } else {
+    if (threadIdx.x == 0 && t == F.first_tile + F.ntiles - 1u &&
+        tile_prefix[t] - tile_prefix[F.first_tile] + tile_total < F.nvar)
+      malformed[F.slot] = 1u;                                // fewer varints than 2 * num_entries
+  }
   if (!term) return;
   k += (uint64_t)__popcll(m & mask_lt(lane_id()));
   if (k >= F.nvar) return;                                    // only the first 2 * num_entries count
-  const uint8_t* reg = files + F.reg_off;
-  uint64_t start = pos;
-  uint32_t len = 1;
-  while (start > 0 && len <= 10u && (reg[start - 1u] & 0x80u)) {
-    start--;
-    len++;
-  }
   const bool is_offset = (k & 1u) != 0;
-  if (len > (is_offset ? 5u : 10u)) {                         // coding.cc:147, 175
+  uint64_t v;
+  bool ok;
+  if (kReversed) ok = ir::varint_ending_at(ir::Reversed{files + F.reg_off}, pos, is_offset, &v);
+  else ok = ir::varint_ending_at(files + F.reg_off, pos, is_offset, &v);
+  if (!ok) {                                                  // coding.cc:147, 175
     malformed[F.slot] = 1u;
     return;
   }
-  uint64_t v = 0;
-  for (uint32_t i = 0; i < len; i++) v |= (uint64_t)(reg[start + i] & 127u) << (7u * i);
   const uint64_t r = F.row_base + (k >> 1);
   if (is_offset) {
     row_off[r] = (uint32_t)v;
@@ -743,6 +761,19 @@ struct kdb_index {
   // open kdb_snapshots: while there are any, the rows keep their sequence
   // numbers (no load) and the handle stays (no destroy)
   uint32_t snapshots = 0;
+  // the tail (include/kdb_index_tail.h): the rows of the writer's open file,
+  // rows [nrows, nrows + tail.rows) of the row arrays and of the buckets, the
+  // file in slot nfiles and rank nloaded of the device arrays.  nrows, nfiles,
+  // nloaded and the host vectors above count the closed files alone: they are
+  // what an add extends and a snapshot takes.
+  struct Tail {
+    bool held = false;
+    uint32_t fileid = 0;
+    uint64_t timestamp = 0, file_off = 0, bytes = 0;
+    uint64_t rows = 0, row_bytes = 0;
+  } tail;
+  uint64_t tail_rows_parsed = 0;         // kdb_index_tail_stats
+  uint64_t visible_rows() const { return nrows + tail.rows; }
 };
 
 // The handle as of kdb_snapshot_create: its first `nrows` rows, `nfiles` file
@@ -799,6 +830,8 @@ void index_release(kdb_index* ix) {
   ix->row_cap = 0;
   ix->add_done = false;
   ix->add_rows_parsed = 0;
+  ix->tail = kdb_index::Tail{};
+  ix->tail_rows_parsed = 0;
 }
 
 // Temporaries of one add, and what it builds beside the handle: the new
@@ -851,6 +884,51 @@ hipError_t upload(hipStream_t st, T** d, const T* h, size_t n) {
 }
 
 enum class Refused { kNo, kTooMany, kOrder };
+
+// Room for nrows rows beside the handle's row arrays, their first `keep` rows
+// copied: the arrays grow geometrically past the handle's capacity (a load
+// sizes them exactly) and the handle keeps its own until the swap.
+hipError_t grow_rows(const kdb_index* ix, hipStream_t st, uint64_t nrows, uint64_t keep, AddTemps* t,
+                     uint64_t* row_cap) {
+  const uint64_t cap = nrows > ix->row_cap ? std::max(nrows, std::min(2u * ix->row_cap, kMaxRows)) : ix->row_cap;
+  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t->d_row_hash), cap * 8u));
+  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t->d_row_off), cap * 4u));
+  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t->d_row_file), cap * 4u));
+  if (keep) {
+    KDB_TRY(hipMemcpyAsync(t->d_row_hash, ix->d_row_hash, keep * 8u, hipMemcpyDeviceToDevice, st));
+    KDB_TRY(hipMemcpyAsync(t->d_row_off, ix->d_row_off, keep * 4u, hipMemcpyDeviceToDevice, st));
+    KDB_TRY(hipMemcpyAsync(t->d_row_file, ix->d_row_file, keep * 4u, hipMemcpyDeviceToDevice, st));
+  }
+  *row_cap = cap;
+  return hipSuccess;
+}
+
+// The buckets over rows [0, nrows) of the given row arrays, into t->d_start
+// and t->d_slots: built from all resident rows, as a load builds them, whether
+// B doubles or stays -- moving the old slots and placing only the new rows was
+// measured and not kept.  The add and the tail share
+// this.  No rows: no buckets, *B = 0 (the lookup asks the row count first).
+hipError_t build_buckets(hipStream_t st, const uint64_t* row_hash, const uint32_t* row_off, const uint32_t* row_file,
+                         uint64_t nrows, AddTemps* t, uint64_t* B_out) {
+  *B_out = 0;
+  if (nrows == 0) return hipSuccess;
+  uint64_t B = 2;
+  while (B < 2u * nrows) B <<= 1;
+  const uint32_t n = (uint32_t)nrows;
+  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t->d_start), (B + 1u) * 8u));
+  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t->d_slots), nrows * sizeof(Slot)));
+  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t->d_count), B * 4u));
+  KDB_TRY(hipMemsetAsync(t->d_count, 0, B * 4u, st));
+  const uint32_t g = std::min<uint32_t>((n + 255u) / 256u, 2048u);
+  hipLaunchKernelGGL(index_hist_kernel, dim3(g), dim3(256), 0, st, row_hash, n, B - 1u, t->d_count);
+  KDB_TRY(hipGetLastError());
+  KDB_TRY(launch_exclusive_scan(st, t->d_count, (uint32_t)B, t->d_start, t->d_start + B));
+  hipLaunchKernelGGL(index_fill_kernel, dim3(g), dim3(256), 0, st, row_hash, row_off, row_file, n, B - 1u,
+                     t->d_start, t->d_count, t->d_slots);
+  KDB_TRY(hipGetLastError());
+  *B_out = B;
+  return hipSuccess;
+}
 
 // The one way rows get into a handle.  The handle holds nfiles files (none:
 // the add is the load); the host arrays describe the nadd new ones, all in
@@ -929,18 +1007,11 @@ hipError_t index_add(kdb_index* ix, hipStream_t st, const uint64_t* file_off, co
     dfree(t.d_malformed);
     const uint32_t ntiles = (uint32_t)tile_file.size();
     if (rows_new == 0 || ntiles == 0) break;
-    if (nrows0 + rows_new > row_cap) {
-      // the row arrays grow geometrically (a load sizes them exactly); the
-      // handle keeps its own until the swap.  Later passes number fewer rows.
-      row_cap = std::max(nrows0 + rows_new, std::min(2u * row_cap, kMaxRows));
-      KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_row_hash), row_cap * 8u));
-      KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_row_off), row_cap * 4u));
-      KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_row_file), row_cap * 4u));
-      if (nrows0) {
-        KDB_TRY(hipMemcpyAsync(t.d_row_hash, ix->d_row_hash, nrows0 * 8u, hipMemcpyDeviceToDevice, st));
-        KDB_TRY(hipMemcpyAsync(t.d_row_off, ix->d_row_off, nrows0 * 4u, hipMemcpyDeviceToDevice, st));
-        KDB_TRY(hipMemcpyAsync(t.d_row_file, ix->d_row_file, nrows0 * 4u, hipMemcpyDeviceToDevice, st));
-      }
+    if (nrows0 + rows_new > row_cap || (ix->tail.rows && !t.d_row_hash)) {
+      // the handle keeps its own arrays until the swap.  Later passes number
+      // fewer rows.  Rows of a tail lie where the new rows go and stay
+      // readable until the swap: the new rows go beside them then
+      KDB_TRY(grow_rows(ix, st, nrows0 + rows_new, nrows0, &t, &row_cap));
       row_hash = t.d_row_hash;
       row_off = t.d_row_off;
       row_file = t.d_row_file;
@@ -951,12 +1022,12 @@ hipError_t index_add(kdb_index* ix, hipStream_t st, const uint64_t* file_off, co
     KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_tile_prefix), ((size_t)ntiles + 1u) * 8u));
     KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_malformed), (size_t)nf * 4u));
     KDB_TRY(hipMemsetAsync(t.d_malformed, 0, (size_t)nf * 4u, st));
-    hipLaunchKernelGGL(index_count_kernel, dim3(ntiles), dim3(kParseTile), 0, st, d_files, t.d_pf, t.d_tile_file,
+    hipLaunchKernelGGL(index_count_kernel<false>, dim3(ntiles), dim3(kParseTile), 0, st, d_files, t.d_pf, t.d_tile_file,
                        t.d_tile_count);
     KDB_TRY(hipGetLastError());
     KDB_TRY(launch_exclusive_scan(st, t.d_tile_count, ntiles, t.d_tile_prefix, t.d_tile_prefix + ntiles));
     // rows [nrows0, nrows0 + rows_new): beyond what the handle's lookups read
-    hipLaunchKernelGGL(index_parse_kernel, dim3(ntiles), dim3(kParseTile), 0, st, d_files, t.d_pf, t.d_tile_file,
+    hipLaunchKernelGGL(index_parse_kernel<false>, dim3(ntiles), dim3(kParseTile), 0, st, d_files, t.d_pf, t.d_tile_file,
                        t.d_tile_prefix, row_hash, row_off, row_file, t.d_malformed);
     KDB_TRY(hipGetLastError());
     rows_parsed += rows_new;
@@ -994,25 +1065,9 @@ hipError_t index_add(kdb_index* ix, hipStream_t st, const uint64_t* file_off, co
 
   const uint64_t nrows = nrows0 + rows_new;
   uint64_t B = ix->nbuckets;
-  if (rows_new) {
-    // the buckets are built again from all resident rows, as a load builds
-    // them, whether B doubles or stays: moving the old slots and placing only
-    // the new rows was measured and not kept
-    B = 2;
-    while (B < 2u * nrows) B <<= 1;
-    const uint32_t n = (uint32_t)nrows;
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_start), (B + 1u) * 8u));
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_slots), nrows * sizeof(Slot)));
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_count), B * 4u));
-    KDB_TRY(hipMemsetAsync(t.d_count, 0, B * 4u, st));
-    const uint32_t g = std::min<uint32_t>((n + 255u) / 256u, 2048u);
-    hipLaunchKernelGGL(index_hist_kernel, dim3(g), dim3(256), 0, st, row_hash, n, B - 1u, t.d_count);
-    KDB_TRY(hipGetLastError());
-    KDB_TRY(launch_exclusive_scan(st, t.d_count, (uint32_t)B, t.d_start, t.d_start + B));
-    hipLaunchKernelGGL(index_fill_kernel, dim3(g), dim3(256), 0, st, row_hash, row_off, row_file, n, B - 1u,
-                       t.d_start, t.d_count, t.d_slots);
-    KDB_TRY(hipGetLastError());
-  }
+  // rows of a tail leave the buckets with it, also where no row comes in
+  const bool rebuild = rows_new || ix->tail.rows;
+  if (rebuild) KDB_TRY(build_buckets(st, row_hash, row_off, row_file, nrows, &t, &B));
   for (uint32_t f = 0; f < nadd; f++) {
     h_ts.push_back(rec[f].timestamp);
     h_type.push_back(rec[f].filetype);
@@ -1026,7 +1081,7 @@ hipError_t index_add(kdb_index* ix, hipStream_t st, const uint64_t* file_off, co
   std::swap(ix->d_fileid, t.d_fileid);
   std::swap(ix->d_file_rank, t.d_file_rank);
   std::swap(ix->d_rank_file, t.d_rank_file);
-  if (rows_new) {
+  if (rebuild) {
     std::swap(ix->d_start, t.d_start);
     std::swap(ix->d_slots, t.d_slots);
   }
@@ -1051,7 +1106,139 @@ hipError_t index_add(kdb_index* ix, hipStream_t st, const uint64_t* file_off, co
   scan_release(&ix->scan);               // the handle's own; a snapshot's list stands on rows that did not move
   ix->add_done = true;
   ix->add_rows_parsed = rows_parsed;
+  ix->tail = kdb_index::Tail{};          // the file that was open arrives closed, or has: its rows are numbered as they were
   *rows_added = rows_new;
+  return hipSuccess;
+}
+
+// kdb_index_set_tail (f) and kdb_index_drop_tail (f == nullptr): the handle's
+// per-file arrays with the open file in the next slot and rank, its staged
+// rows parsed behind the closed files' rows, the buckets over all of them;
+// built beside the handle and swapped in at the end, like an add.
+hipError_t index_tail(kdb_index* ix, hipStream_t st, const kdb_open_file* f, bool reparse, uint64_t* gained,
+                      bool* refused) {
+  const kdb_index::Tail held = ix->tail;
+  if (!f && !held.held) return hipSuccess;
+  const bool grows = f && held.held && held.fileid == f->fileid;
+  const bool incremental = grows && !reparse;
+  const uint32_t nf0 = ix->nfiles, nf = nf0 + (f ? 1u : 0u);
+  const uint64_t nrows0 = ix->nrows, trows = f ? f->rows : 0u, nrows = nrows0 + trows;
+  const uint64_t hr = incremental ? held.rows : 0u, hb = incremental ? held.row_bytes : 0u;
+  if (f) {
+    *refused = true;
+    if (nf0 == 0xFFFFFFFFu || f->bytes > hs::kMaxFileSize || f->rows > kMaxRows || nrows > kMaxRows) return hipSuccess;
+    // an open file only grows, where it lies
+    if (grows && (f->rows < held.rows || f->row_bytes < held.row_bytes || f->bytes < held.bytes ||
+                  f->file_off != held.file_off || f->timestamp != held.timestamp))
+      return hipSuccess;
+    if (!ir::tail_range_ok(hr, hb, f->rows, f->row_bytes, f->rows_last)) return hipSuccess;
+    // it closes after every loaded file: index_add's order rule, ahead of time
+    for (uint32_t o = 0; o < nf0; o++)
+      if (ix->status[o] == 0 && (f->timestamp < ix->timestamp[o] ||
+                                 (f->timestamp == ix->timestamp[o] && f->fileid <= ix->fileid[o])))
+        return hipSuccess;
+    *refused = false;
+    if (incremental && f->rows == held.rows && f->row_bytes == held.row_bytes && f->bytes == held.bytes) {
+      ix->tail_rows_parsed = 0;            // nothing was appended: nothing changes
+      *gained = 0;
+      return hipSuccess;
+    }
+  }
+  // host arrays first, the device temporaries after them (see index_add)
+  std::vector<uint64_t> h_off(ix->file_off), h_size(ix->file_size);
+  std::vector<uint32_t> h_id(ix->fileid), rank(ix->rank), rank_file(ix->rank_file);
+  uint32_t bad = 0;
+  AddTemps t;
+  if (f) {
+    h_off.push_back(f->file_off);
+    h_size.push_back(f->bytes);
+    h_id.push_back(f->fileid);
+    rank.push_back(ix->nloaded);
+    rank_file.resize(nf, 0u);
+    rank_file[ix->nloaded] = nf0;
+  }
+  KDB_TRY(upload(st, &t.d_file_off, h_off.data(), nf));
+  KDB_TRY(upload(st, &t.d_file_size, h_size.data(), nf));
+  KDB_TRY(upload(st, &t.d_fileid, h_id.data(), nf));
+  KDB_TRY(upload(st, &t.d_file_rank, rank.data(), nf));
+  KDB_TRY(upload(st, &t.d_rank_file, rank_file.data(), nf));
+
+  uint64_t* row_hash = ix->d_row_hash;
+  uint32_t* row_off = ix->d_row_off;
+  uint32_t* row_file = ix->d_row_file;
+  uint64_t row_cap = ix->row_cap;
+  const uint64_t parsed = trows - hr;
+  if (parsed) {
+    // rows [nrows0 + hr, nrows): in place only where they lie beyond every
+    // row the handle's lookups and scans read now
+    if (!incremental || nrows > row_cap) {
+      KDB_TRY(grow_rows(ix, st, nrows, nrows0 + hr, &t, &row_cap));
+      row_hash = t.d_row_hash;
+      row_off = t.d_row_off;
+      row_file = t.d_row_file;
+    }
+    ParseFile p{};
+    p.reg_len = f->row_bytes - hb;         // >= 2 * parsed
+    p.reg_off = f->rows_last - hb;         // staged byte hb; the range ends at rows_last - (row_bytes - 1) >= 0
+    p.nvar = 2u * parsed;
+    p.row_base = nrows0 + hr;
+    p.first_tile = 0;
+    p.ntiles = (uint32_t)((p.reg_len + kParseTile - 1u) / kParseTile);   // reg_len <= 15 * 2^30
+    p.slot = nf0;
+    const uint32_t ntiles = p.ntiles;
+    KDB_TRY(upload(st, &t.d_pf, &p, 1));
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_tile_file), (size_t)ntiles * 4u));
+    KDB_TRY(hipMemsetAsync(t.d_tile_file, 0, (size_t)ntiles * 4u, st));
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_tile_count), (size_t)ntiles * 4u));
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_tile_prefix), ((size_t)ntiles + 1u) * 8u));
+    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_malformed), (size_t)nf * 4u));
+    KDB_TRY(hipMemsetAsync(t.d_malformed, 0, (size_t)nf * 4u, st));
+    hipLaunchKernelGGL(index_count_kernel<true>, dim3(ntiles), dim3(kParseTile), 0, st, ix->d_files, t.d_pf,
+                       t.d_tile_file, t.d_tile_count);
+    KDB_TRY(hipGetLastError());
+    KDB_TRY(launch_exclusive_scan(st, t.d_tile_count, ntiles, t.d_tile_prefix, t.d_tile_prefix + ntiles));
+    hipLaunchKernelGGL(index_parse_kernel<true>, dim3(ntiles), dim3(kParseTile), 0, st, ix->d_files, t.d_pf,
+                       t.d_tile_file, t.d_tile_prefix, row_hash, row_off, row_file, t.d_malformed);
+    KDB_TRY(hipGetLastError());
+    KDB_TRY(hipMemcpyAsync(&bad, t.d_malformed + nf0, 4u, hipMemcpyDeviceToHost, st));
+    KDB_TRY(hipStreamSynchronize(st));
+    if (bad) {                             // not two varints per row, or one too long
+      *refused = true;
+      return hipSuccess;
+    }
+  }
+  uint64_t B = 0;
+  KDB_TRY(build_buckets(st, row_hash, row_off, row_file, nrows, &t, &B));
+  KDB_TRY(hipStreamSynchronize(st));
+
+  // nothing can fail any more
+  std::swap(ix->d_file_off, t.d_file_off);
+  std::swap(ix->d_file_size, t.d_file_size);
+  std::swap(ix->d_fileid, t.d_fileid);
+  std::swap(ix->d_file_rank, t.d_file_rank);
+  std::swap(ix->d_rank_file, t.d_rank_file);
+  std::swap(ix->d_start, t.d_start);
+  std::swap(ix->d_slots, t.d_slots);
+  if (t.d_row_hash) {
+    std::swap(ix->d_row_hash, t.d_row_hash);
+    std::swap(ix->d_row_off, t.d_row_off);
+    std::swap(ix->d_row_file, t.d_row_file);
+    ix->row_cap = row_cap;
+  }
+  ix->nbuckets = B;
+  ix->tail = kdb_index::Tail{};
+  if (f) {
+    ix->tail.held = true;
+    ix->tail.fileid = f->fileid;
+    ix->tail.timestamp = f->timestamp;
+    ix->tail.file_off = f->file_off;
+    ix->tail.bytes = f->bytes;
+    ix->tail.rows = f->rows;
+    ix->tail.row_bytes = f->row_bytes;
+  }
+  ix->tail_rows_parsed = parsed;
+  scan_release(&ix->scan);                 // the handle's own; a snapshot's list stands on rows below its limit
+  *gained = grows ? trows - held.rows : trows;
   return hipSuccess;
 }
 
@@ -1104,7 +1291,8 @@ extern "C" int kdb_index_add_files(kdb_index* ix, void* stream, const uint8_t* d
     return KDB_PUT_EINVAL;
   if (entries_added_out) *entries_added_out = 0;
   if (nadd == 0) return KDB_PUT_OK;
-  if (nadd > 0xFFFFFFFFu - ix->nfiles || (ix->nfiles && d_files != ix->d_files)) return KDB_PUT_EINVAL;
+  if (nadd > 0xFFFFFFFFu - ix->nfiles || ((ix->nfiles || ix->tail.held) && d_files != ix->d_files))
+    return KDB_PUT_EINVAL;
   for (uint32_t f = 0; f < nadd; f++)
     if (file_size[f] > hs::kMaxFileSize) return KDB_PUT_EINVAL;
   const uint8_t* held = ix->d_files;
@@ -1129,6 +1317,46 @@ extern "C" int kdb_index_add_stats(const kdb_index* ix, uint32_t* merged, uint64
   return KDB_PUT_OK;
 }
 
+extern "C" int kdb_index_set_tail(kdb_index* ix, void* stream, const uint8_t* d_files, const kdb_open_file* f,
+                                  uint32_t flags, uint64_t* rows_added_out) {
+  if (rows_added_out) *rows_added_out = 0;
+  if (!ix || !f || (flags & ~KDB_INDEX_TAIL_REPARSE)) return KDB_PUT_EINVAL;
+  const bool none = !f->open || f->incomplete;
+  if (!none && (!d_files || ((ix->nfiles || ix->tail.held) && d_files != ix->d_files))) return KDB_PUT_EINVAL;
+  const uint8_t* held = ix->d_files;
+  if (!none) ix->d_files = d_files;      // a handle without files adopts the buffer
+  bool refused = false;
+  uint64_t gained = 0;
+  const hipError_t e = index_tail(ix, (hipStream_t)stream, none ? nullptr : f, (flags & KDB_INDEX_TAIL_REPARSE) != 0,
+                                  &gained, &refused);
+  if (e != hipSuccess || refused) {
+    ix->d_files = held;
+    return e != hipSuccess ? hip_code(e) : KDB_PUT_EINVAL;
+  }
+  if (none) ix->tail_rows_parsed = 0;
+  if (rows_added_out) *rows_added_out = gained;
+  return KDB_PUT_OK;
+}
+
+extern "C" int kdb_index_drop_tail(kdb_index* ix, void* stream) {
+  if (!ix) return KDB_PUT_EINVAL;
+  bool refused = false;
+  uint64_t gained = 0;
+  return hip_code(index_tail(ix, (hipStream_t)stream, nullptr, false, &gained, &refused));
+}
+
+extern "C" int kdb_index_tail_stats(const kdb_index* ix, uint32_t* held, uint32_t* fileid, uint64_t* rows,
+                                    uint64_t* bytes, uint64_t* rows_parsed_last, uint64_t* nbuckets) {
+  if (!ix || !held) return KDB_PUT_EINVAL;
+  *held = ix->tail.held ? 1u : 0u;
+  if (fileid) *fileid = ix->tail.fileid;
+  if (rows) *rows = ix->tail.rows;
+  if (bytes) *bytes = ix->tail.bytes;
+  if (rows_parsed_last) *rows_parsed_last = ix->tail_rows_parsed;
+  if (nbuckets) *nbuckets = ix->nbuckets;
+  return KDB_PUT_OK;
+}
+
 // kdb_compact.h: the timestamp the compacted files lock (storage_engine.h:806-810, 927-934)
 extern "C" int kdb_index_view_timestamp(const kdb_index* ix, uint32_t nfiles, uint64_t* timestamp_max) {
   if (!ix || !timestamp_max || nfiles > ix->nfiles) return KDB_PUT_EINVAL;
@@ -1144,22 +1372,23 @@ extern "C" int kdb_index_view_timestamp(const kdb_index* ix, uint32_t nfiles, ui
 
 extern "C" int kdb_index_entry_count(const kdb_index* ix, uint64_t* count) {
   if (!ix || !count) return KDB_PUT_EINVAL;
-  *count = ix->nrows;
+  *count = ix->visible_rows();
   return KDB_PUT_OK;
 }
 
 extern "C" int kdb_index_pairs(const kdb_index* ix, uint64_t* hash_out, uint64_t* location_out) {
-  if (!ix || (ix->nrows && (!hash_out || !location_out))) return KDB_PUT_EINVAL;
-  if (ix->nrows == 0) return KDB_PUT_OK;
-  const size_t n = (size_t)ix->nrows;
+  if (!ix || (ix->visible_rows() && (!hash_out || !location_out))) return KDB_PUT_EINVAL;
+  if (ix->visible_rows() == 0) return KDB_PUT_OK;
+  const size_t n = (size_t)ix->visible_rows();
   std::vector<uint32_t> off(n), file(n);
   hipError_t e = hipMemcpy(hash_out, ix->d_row_hash, n * 8u, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(off.data(), ix->d_row_off, n * 4u, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(file.data(), ix->d_row_file, n * 4u, hipMemcpyDeviceToHost);
   if (e != hipSuccess) return hip_code(e);
   for (size_t r = 0; r < n; r++) {
-    if (file[r] >= ix->nfiles) return KDB_PUT_EHIP;
-    location_out[r] = (uint64_t)ix->fileid[file[r]] << 32 | off[r];
+    if (file[r] >= ix->nfiles + (ix->tail.held ? 1u : 0u)) return KDB_PUT_EHIP;
+    const uint32_t id = file[r] < ix->nfiles ? ix->fileid[file[r]] : ix->tail.fileid;   // the tail's slot is the next one
+    location_out[r] = (uint64_t)id << 32 | off[r];
   }
   return KDB_PUT_OK;
 }
@@ -1188,7 +1417,7 @@ int lookup_batch(const kdb_index* ix, const kdb_snapshot* snap, void* stream, co
   uint32_t* slot_len = reinterpret_cast<uint32_t*>(scratch);
   // a snapshot: the handle's arrays as they are now, the row count its own limit
   const IndexView view{ix->d_files,  ix->d_file_off, ix->d_file_size,        ix->d_fileid, ix->d_start,
-                       ix->d_slots,  ix->nbuckets ? ix->nbuckets - 1u : 0u, (uint32_t)(snap ? snap->nrows : ix->nrows),
+                       ix->d_slots,  ix->nbuckets ? ix->nbuckets - 1u : 0u, (uint32_t)(snap ? snap->nrows : ix->visible_rows()),
                        ix->hash_type};
   const uint32_t waves = kGetBlock / 64;
   const uint32_t g = std::min<uint32_t>((n + waves - 1u) / waves, 16384u);
@@ -1384,7 +1613,7 @@ int scan_batch(const kdb_index* ix, const ScanState* sc, uint64_t nrows, void* s
 extern "C" int kdb_index_scan_prepare(kdb_index* ix, void* stream, int verify_header, uint64_t* live,
                                       uint64_t* key_bytes, uint32_t* max_key_len) {
   if (!ix || verify_header < 0 || verify_header > 1) return KDB_PUT_EINVAL;
-  return scan_prepare_checked(ix, &ix->scan, ix->nrows, false, stream, verify_header, live, key_bytes, max_key_len);
+  return scan_prepare_checked(ix, &ix->scan, ix->visible_rows(), false, stream, verify_header, live, key_bytes, max_key_len);
 }
 
 extern "C" int kdb_index_scan_sort_steps(const kdb_index* ix, uint32_t* steps) {
@@ -1402,7 +1631,7 @@ extern "C" int kdb_index_scan_batch(const kdb_index* ix, void* stream, uint64_t 
                                     uint32_t* checksum, uint32_t* checksum_initial, uint64_t* out_off,
                                     uint64_t* location, int32_t* status, uint64_t* summary) {
   if (!ix) return KDB_PUT_EINVAL;
-  return scan_batch(ix, &ix->scan, ix->nrows, stream, first, n, multipart_required, scratch, scratch_bytes, keys_out,
+  return scan_batch(ix, &ix->scan, ix->visible_rows(), stream, first, n, multipart_required, scratch, scratch_bytes, keys_out,
                     keys_cap, key_off, key_len, stored_off, avail, svc, size, checksum, checksum_initial, out_off,
                     location, status, summary);
 }

@@ -25,6 +25,9 @@ set of closed HSTable files and the batched lookup in front of the decoder.
   .refresh()              adds the files the writer has closed since
                           (kdb_index_add_files; StorageEngine::ProcessingLoopIndex):
                           write -> refresh -> get, with no file loaded twice
+  .refresh(tail=True)     the same, and then the rows of the file the writer
+                          still has open (kdb_index_set_tail): every put of an
+                          appended batch can be read, with no file cut short
   .snapshot()             an HSTableSnapshot: get, locate, scan, items, compacted
                           and compacted_device as of now, while refresh() and
                           add_files() go on (kdb_snapshot_*; Database::NewSnapshot)
@@ -53,6 +56,7 @@ from .lz4 import DeviceBuffer, Stream
 
 NOTFOUND, DELETED, MULTIPART = -3, -4, -5
 FILE_ORDER = -4                  # file status KDB_INDEX_FILE_ORDER: not newer than the loaded files
+TAIL_REPARSE = 1                 # KDB_INDEX_TAIL_REPARSE
 MULTIPART_REQUIRED = 1 << 20     # internal__size_multipart_required
 
 
@@ -421,6 +425,7 @@ class _ReadPath:
         ts = ctypes.c_uint64(0)
         ih, nfiles = self._view()
         _lib.check(lib().kdb_index_view_timestamp(ih, nfiles, ctypes.byref(ts)), "kdb_index_view_timestamp")
+        ts.value = max(ts.value, self._tail_timestamp())      # an index's tail is a file of its view
         nmax = max([n for _, n in windows], default=1)
         L = _Lookup(nmax, nmax * kmax)
         bufs = [L]
@@ -477,6 +482,10 @@ class _ReadPath:
                 b.free()
         return w
 
+    def _tail_timestamp(self) -> int:
+        """The timestamp of the open file a view includes, 0 where it includes none."""
+        return 0
+
     def _compact_fail(self, L: _Lookup, n: int, decoded: bool) -> None:
         """The error compacted() raises, for the window's first value that does not decode."""
         status = L.meta.download(4 * n, L.off["status"], dtype=np.int32)
@@ -493,6 +502,7 @@ class _ReadPath:
 
 class HSTableIndex(_ReadPath):
     _snapshots = None                    # the open HSTableSnapshots, once there was one
+    _tail = None                         # {"fileid", "rows", "bytes"} of the writer's open file, while held
     def __init__(self, files: dict[str, bytes], hash_type: int = 1, stream: Stream | None = None,
                  recover: str | None = None, reserve: int = 0):
         from . import recover as rec
@@ -620,6 +630,9 @@ class HSTableIndex(_ReadPath):
             refused = [f for f, s in zip(names, status[:n]) if s == FILE_ORDER]
             _lib.check(rc, "kdb_index_add_files" + (f" (not newer than the loaded files: {refused})" if refused else ""))
         self._scan = None
+        if n:                            # the tail, where one was held, is dropped by the add
+            self.entries -= self._tail["rows"] if self._tail else 0
+            self._tail = None
         self.names += names
         self.file_off = np.concatenate([self.file_off, off])
         self.file_size = np.concatenate([self.file_size, size])
@@ -629,24 +642,80 @@ class HSTableIndex(_ReadPath):
         self.entries += added.value
         return res
 
-    def refresh(self, stream: Stream | None = None) -> int:
+    def refresh(self, stream: Stream | None = None, tail: bool = False, reparse: bool = False) -> int:
         """For an index made by from_resident(): adds the files its writer has
         closed since the index last looked (kdb_index_add_files, the part of
         StorageEngine::ProcessingLoopIndex a flush triggers) and returns the
-        rows added.  Files already held are not read again.  Entries of the
-        writer's still open file are not readable before it closes.  A
-        prepared scan is dropped (the next scan prepares again).  Not to run
+        rows added.  Files already held are not read again.  With tail=False
+        entries of the writer's still open file are not readable before it
+        closes.  With tail=True the rows of that file are indexed as well,
+        from where the writer stages them (kdb_index_set_tail; only the rows
+        appended since the last such refresh are parsed, all of them with
+        reparse=True): every entry of every appended batch is readable, and
+        the index answers as one made fresh over the closed files and the
+        open file closed as it is now.  Where no file is open, or the open
+        file is incomplete (the last part of a multipart value has not
+        arrived: it would close without an offset array), the tail is
+        dropped.  The return value counts the tail's growth too.  A prepared
+        scan is dropped (the next scan prepares again).  Not to run
         concurrently with lookups on this index."""
         if self._owner is None:
             raise ValueError("refresh() is for an index made by from_resident(); use add_files()")
+        st = stream.ptr if stream else None
         ptr, off, size, fid = self._owner.resident()
         held = {int(f) for f in self.fileid}
         new = [i for i in range(len(fid)) if int(fid[i]) not in held]
-        if not new:
-            return 0
         before = self.entries
-        self._add(stream.ptr if stream else None, off[new], size[new], fid[new])
+        if new:
+            self._add(st, off[new], size[new], fid[new])
+        if tail:
+            f = self._owner.open_file()
+            self.set_tail(f if f is not None else _lib.OpenFile(), st, TAIL_REPARSE if reparse else 0)
         return self.entries - before
+
+    def set_tail(self, f, st=None, flags: int = 0) -> int:
+        """kdb_index_set_tail of an _lib.OpenFile record that lies in
+        self.files: the rows the tail gained.  The index changes only if the
+        call succeeds (HipError EINVAL otherwise)."""
+        gained = ctypes.c_uint64(0)
+        _lib.check(lib().kdb_index_set_tail(self.h, st, self.files.ptr, ctypes.byref(f), flags, ctypes.byref(gained)),
+                   "kdb_index_set_tail")
+        self._sync_tail()
+        return gained.value
+
+    def drop_tail(self, stream: Stream | None = None) -> None:
+        """The index over the closed files alone again (kdb_index_drop_tail)."""
+        _lib.check(lib().kdb_index_drop_tail(self.h, stream.ptr if stream else None), "kdb_index_drop_tail")
+        self._sync_tail()
+
+    def _sync_tail(self) -> None:
+        held, fid, rows, nbytes, _, _ = self.tail_stats()
+        self._tail = {"fileid": fid, "rows": rows, "bytes": nbytes} if held else None
+        self._scan = None                # the C side drops the prepared scan with every change of the tail
+        n = ctypes.c_uint64(0)
+        _lib.check(lib().kdb_index_entry_count(self.h, ctypes.byref(n)), "kdb_index_entry_count")
+        self.entries = n.value
+
+    @property
+    def tail(self):
+        """None, or {"fileid", "rows", "bytes"} of the writer's open file as
+        the index holds it (refresh(tail=True)).  `entries` counts its rows;
+        names, file_status, file_off, file_size and fileid list the closed
+        files alone."""
+        return dict(self._tail) if self._tail else None
+
+    def tail_stats(self) -> tuple[int, int, int, int, int, int]:
+        """(held, fileid, rows, bytes, rows parsed by the last set_tail, buckets): kdb_index_tail_stats."""
+        held, fid = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        rows, nbytes, parsed, nb = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _lib.check(lib().kdb_index_tail_stats(self.h, ctypes.byref(held), ctypes.byref(fid), ctypes.byref(rows),
+                                              ctypes.byref(nbytes), ctypes.byref(parsed), ctypes.byref(nb)),
+                   "kdb_index_tail_stats")
+        return held.value, fid.value, rows.value, nbytes.value, parsed.value, nb.value
+
+    def _tail_timestamp(self) -> int:
+        f = self._owner.open_file() if self._tail and self._owner is not None else None
+        return f.timestamp if f is not None and f.fileid == self._tail["fileid"] else 0
 
     def add_files(self, files: dict[str, bytes], stream: Stream | None = None) -> dict[str, int]:
         """Uploads `files` into the room HSTableIndex(..., reserve=) left behind
@@ -741,8 +810,9 @@ class HSTableIndex(_ReadPath):
         Database::NewSnapshot): its get, locate, scan, items and compaction go
         on answering over the files held at this moment while refresh() /
         add_files() add newer ones.  It copies nothing and costs no device
-        work.  Entries of the writer's still open file are in neither; close
-        or cut the file and refresh() first to have them in the snapshot.
+        work.  Entries of the writer's still open file are not in a snapshot,
+        also where refresh(tail=True) has made them readable through the
+        index; close or cut the file and refresh() first to have them in it.
         close() it, or use it as a context manager; close() of the index
         closes the snapshots still open."""
         return HSTableSnapshot(self)

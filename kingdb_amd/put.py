@@ -383,6 +383,15 @@ class DeviceHSTableWriter:
         _lib.check(lib().kdb_hstable_dev_open_bytes(self.h, ctypes.byref(b)), "hstable_dev_open_bytes")
         return b.value
 
+    def open_file(self):
+        """The file that is open, as HSTableIndex.refresh(tail=True) reads it
+        (kdb_hstable_dev_open_file): an _lib.OpenFile record -- fileid,
+        incomplete, timestamp, file_off, bytes, rows, row_bytes, rows_last --
+        or None where no file is open.  Waits for the writer's queued work."""
+        f = _lib.OpenFile()
+        _lib.check(lib().kdb_hstable_dev_open_file(self.h, ctypes.byref(f)), "hstable_dev_open_file")
+        return f if f.open else None
+
     def adopt(self, first_fileid: int, src_ptr: int, off, size, fileid, stream: Stream | None = None) -> None:
         """The hand-over of a compaction (kdb_hstable_dev_adopt): the writer's
         own closed files become first_fileid, first_fileid + 1, ...; the files
