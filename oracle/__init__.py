@@ -258,10 +258,12 @@ class Reference:
         r = self.lib.ref_compress_limited(_ptr(src), _ptr(dst), len(data), cap)
         return None if r == 0 else dst[:r].tobytes()
 
-    def decompress(self, block: bytes, size: int) -> tuple[int, bytes]:
+    def decompress(self, block: bytes, size: int, target: int | None = None) -> tuple[int, bytes]:
+        """LZ4_decompress_safe_partial(block, dst, len(block), target, size); target defaults to size."""
         src = np.frombuffer(block, dtype=np.uint8).copy() if len(block) else np.zeros(1, np.uint8)
         dst = np.zeros(size + 64, dtype=np.uint8)
-        r = self.lib.ref_decompress_partial(_ptr(src), len(block), _ptr(dst), size, size)
+        r = self.lib.ref_decompress_partial(_ptr(src), len(block), _ptr(dst), size if target is None else target,
+                                            size)
         return r, (dst[:r].tobytes() if r > 0 else b"")
 
     def frame(self, data: bytes) -> bytes:
