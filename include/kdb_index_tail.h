@@ -68,7 +68,9 @@ int kdb_hstable_dev_open_file(const struct kdb_hstable_dev* w, struct kdb_open_f
  * do not hold exactly two varints per row, a hash of more than 10 bytes or an
  * offset of more than 5; a range outside d_files as far as the record tells
  * (rows_last < row_bytes - 1); more than 2^30 rows in all.  A successful call
- * drops a prepared scan.  Snapshots do not see the tail and may be open.
+ * drops a prepared scan.  Snapshots of kdb_snapshot_create do not see the tail
+ * and may be open; one of kdb_snapshot_create_tail (include/kdb_live.h) holds
+ * the tail to the file it took until that file has been added closed.
  * *rows_added_out = the rows the tail gained: all of a new tail's, those
  * beyond the rows held of a tail that grew (may be NULL). */
 int kdb_index_set_tail(struct kdb_index* ix, void* stream, const uint8_t* d_files, const struct kdb_open_file* f,

@@ -154,6 +154,11 @@ SIGNATURES = {
     "kdb_index_drop_tail": (_i, [_vp, _vp]),
     "kdb_index_tail_stats": (_i, [_vp, _c.POINTER(_u32), _c.POINTER(_u32), _c.POINTER(_u64), _c.POINTER(_u64),
                                   _c.POINTER(_u64), _c.POINTER(_u64)]),
+    # include/kdb_live.h (snapshots and the hand-over over the open file)
+    "kdb_snapshot_create_tail": (_i, [_vp, _c.POINTER(_vp)]),
+    "kdb_snapshot_tail_stats": (_i, [_vp, _c.POINTER(_u32), _c.POINTER(_u32), _c.POINTER(_u64), _c.POINTER(_u32)]),
+    "kdb_snapshot_scan_closed_live": (_i, [_vp, _c.POINTER(_u64)]),
+    "kdb_hstable_dev_adopt_open": (_i, [_vp, _vp, _vp]),
     # include/kdb_recover.h (files without a usable footer, recovered in device memory)
     "kdb_hstable_recover_bound": (_u64, [_u64]),
     "kdb_hstable_recover_scratch_bytes": (_u64, [_vp, _u32]),

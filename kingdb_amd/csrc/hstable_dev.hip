@@ -353,7 +353,12 @@ struct kdb_hstable_dev {
   uint64_t open_rows = 0;                 // its rows so far
   uint64_t staged = 0;                    // and their bytes, staged at the arena's end
   uint64_t next_off = 0;                  // the end of the last closed file
-  uint32_t fileid = 0;
+  uint32_t fileid = 0;                    // the largest id given out
+  // the open file's id and header timestamp: fileid and the timestamp of its
+  // day, unless the file was carried in from another writer
+  // (kdb_hstable_dev_adopt_open, kdb_live.h) and keeps its own
+  uint32_t open_id = 0;
+  uint64_t open_ts = 0;
   // kdb_hstable_dev_create2 (kdb_compact.h): the type of the files written and,
   // where nonzero, the timestamp every header carries instead of the file's id
   // (LockSequenceTimestamp).  kdb_hstable_dev_adopt returns both to 1 and 0.
@@ -433,7 +438,8 @@ struct Placement {
   std::vector<Place> places;
   cut::State st;
   uint64_t open_base, open_rows, staged, next_off;
-  uint32_t fileid;
+  uint32_t fileid, open_id;
+  uint64_t open_ts;
   std::vector<uint64_t> file_off, file_size;
   std::vector<uint32_t> file_id;
   uint64_t unstage_dst = 0, unstage_bytes = 0;
@@ -447,6 +453,8 @@ bool place_records(const kdb_hstable_dev* w, const cut::FileRec* recs, uint32_t 
   p.staged = w->staged;
   p.next_off = w->next_off;
   p.fileid = w->fileid;
+  p.open_id = w->open_id;
+  p.open_ts = w->open_ts;
   uint64_t max_extent = 0, max_staged = w->staged;
   const uint64_t lim = w->arena_bytes;
   for (uint32_t r = 0; r < nrec; r++) {
@@ -458,7 +466,9 @@ bool place_records(const kdb_hstable_dev* w, const cut::FileRec* recs, uint32_t 
       p.open_rows = 0;
       p.staged = 0;
       p.fileid++;
-      file_header(w, w->ts_lock ? w->ts_lock : p.fileid, pl.hdr);     // timestamps count with the ids, unless locked
+      p.open_id = p.fileid;
+      p.open_ts = w->ts_lock ? w->ts_lock : p.fileid;                 // timestamps count with the ids, unless locked
+      file_header(w, p.open_ts, pl.hdr);
     } else if (r != 0 || !p.st.open || f.fs != p.st.fsize) {
       return false;                         // only the first record continues a file
     }
@@ -486,7 +496,7 @@ bool place_records(const kdb_hstable_dev* w, const cut::FileRec* recs, uint32_t 
       extent = p.open_base + size;
       p.file_off.push_back(p.open_base);
       p.file_size.push_back(size);
-      p.file_id.push_back(p.fileid);
+      p.file_id.push_back(p.open_id);
       p.next_off = extent;
       p.st = cut::State{0, 0, 0, 0, 0};
       p.staged = 0;
@@ -517,6 +527,8 @@ void commit(kdb_hstable_dev* w, const Placement& p) {
   w->staged = p.staged;
   w->next_off = p.next_off;
   w->fileid = p.fileid;
+  w->open_id = p.open_id;
+  w->open_ts = p.open_ts;
   w->file_off.insert(w->file_off.end(), p.file_off.begin(), p.file_off.end());
   w->file_size.insert(w->file_size.end(), p.file_size.begin(), p.file_size.end());
   w->file_id.insert(w->file_id.end(), p.file_id.begin(), p.file_id.end());
@@ -748,9 +760,9 @@ extern "C" int kdb_hstable_dev_open_file(const kdb_hstable_dev* w, kdb_open_file
   *out = kdb_open_file{};
   if (!w->st.open) return KDB_PUT_OK;
   out->open = 1u;
-  out->fileid = w->fileid;
+  out->fileid = w->open_id;
   out->incomplete = w->st.incomplete ? 1u : 0u;
-  out->timestamp = w->ts_lock ? w->ts_lock : w->fileid;
+  out->timestamp = w->open_ts;
   out->file_off = w->open_base;
   out->bytes = w->st.fsize;
   out->rows = w->open_rows;
@@ -776,6 +788,8 @@ extern "C" int kdb_hstable_dev_reset(kdb_hstable_dev* w) {
   w->st = cut::State{0, 0, 0, 0, 0};
   w->open_base = w->open_rows = w->staged = w->next_off = 0;
   w->fileid = 0;
+  w->open_id = 0;
+  w->open_ts = 0;
   w->file_off.clear();
   w->file_size.clear();
   w->file_id.clear();
@@ -833,6 +847,48 @@ extern "C" int kdb_hstable_dev_adopt(kdb_hstable_dev* w, void* stream, uint32_t 
   w->fileid = first_fileid + (uint32_t)own - 1u;      // above the adopted ids too: they are below first_fileid
   w->filetype = 1u;
   w->ts_lock = 0u;
+  return KDB_PUT_OK;
+}
+
+// kdb_live.h: the hand-over's last step, the open file itself
+extern "C" int kdb_hstable_dev_adopt_open(kdb_hstable_dev* dst, void* stream, const kdb_hstable_dev* src) {
+  if (!dst || !src || dst == src) return KDB_PUT_EINVAL;
+  if (!src->st.open) return KDB_PUT_OK;
+  if (dst->st.open || dst->sb != src->sb || dst->hash_type != src->hash_type) return KDB_PUT_EINVAL;
+  if (dst->filetype != 1u || dst->ts_lock || src->filetype != 1u || src->ts_lock) return KDB_PUT_EINVAL;
+  const uint32_t id = src->open_id;
+  if (id == 0) return KDB_PUT_EINVAL;
+  for (uint32_t held : dst->file_id)
+    if (held == id) return KDB_PUT_EINVAL;
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(dst->arena), a1 = a0 + dst->arena_bytes;
+  const uintptr_t s0 = reinterpret_cast<uintptr_t>(src->arena), s1 = s0 + src->arena_bytes;
+  if (s0 < a1 && a0 < s1) return KDB_PUT_EINVAL;
+  // what place_records() asks of an open file: the files from the arena's
+  // start and the staging from its end never meet
+  const uint64_t fsize = src->st.fsize, staged = src->st.incomplete ? 0u : src->staged;
+  const uint64_t base = align64(dst->next_off);
+  if (src->open_base > src->arena_bytes || fsize > src->arena_bytes - src->open_base || staged > src->arena_bytes)
+    return KDB_PUT_EINVAL;
+  if (base > dst->arena_bytes || fsize > dst->arena_bytes - base || staged > dst->arena_bytes - base - fsize)
+    return KDB_PUT_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = st != src->last ? hipStreamSynchronize(src->last) : hipSuccess;
+  if (e == hipSuccess && st != dst->last && dst->last != src->last) e = hipStreamSynchronize(dst->last);
+  if (e == hipSuccess && fsize)
+    e = hipMemcpyAsync(dst->arena + base, src->arena + src->open_base, fsize, hipMemcpyDeviceToDevice, st);
+  // staged byte b lies at arena[arena_bytes - 1 - b] in both: the block as it is
+  if (e == hipSuccess && staged)
+    e = hipMemcpyAsync(dst->arena + (dst->arena_bytes - staged), src->arena + (src->arena_bytes - staged), staged,
+                       hipMemcpyDeviceToDevice, st);
+  if (e != hipSuccess) return hip_code(e);   // bytes behind next_off are nobody's: the writer is as before
+  dst->last = st;
+  dst->st = src->st;
+  dst->open_base = base;
+  dst->open_rows = src->open_rows;
+  dst->staged = staged;
+  dst->open_id = id;
+  dst->open_ts = src->open_ts;
+  dst->fileid = std::max(dst->fileid, id);   // files opened later: one above every id held
   return KDB_PUT_OK;
 }
 

@@ -50,6 +50,10 @@
 // handle's current buckets, answer as a handle loaded over the files held
 // then: index_get_kernel<true>, index_live_kernel<true>, and the scan's other
 // kernels over the snapshot's own list
+// Tail snapshot (include/kdb_live.h): R also counts the rows of the open file
+// held as the tail.  The same kernels; the handle keeps those rows in place
+// while such a snapshot is open (csrc/live_pin.h), and when the file arrives
+// closed index_rows_equal_kernel checks that its first rows are the rows held
 // Scan (include/kdb_scan.h; Database::NewIterator, interface/iterator.h:112-214):
 //   index_live_kernel    wave per row: the row is live iff the lookup of its
 //                        own stored key would select it (prepare, synchronous)
@@ -77,10 +81,12 @@
 #include "hip_host.h"
 #include "hstable_decode.h"
 #include "index_rows.h"
+#include "live_pin.h"
 #include "lz4_device.h"
 
 namespace hs = kdb_hstable;
 namespace ir = kdb_index_rows;
+namespace lp = kdb_live_pin;
 
 namespace kdb_lz4 {
 namespace {
@@ -277,6 +283,19 @@ __global__ void index_fill_kernel(const uint64_t* __restrict__ row_hash, const u
     const uint32_t at = atomicSub(&count[b], 1u) - 1u;
     slots[start[b] + at] = Slot{h, row_file[r], row_off[r], r, 0u};
   }
+}
+
+// The pin's check (include/kdb_live.h): rows [0, n) of the two row arrays --
+// the rows the handle holds of the open file, and the same file's rows parsed
+// again from its closed form -- must be equal, hash and offset.  One flag.
+__global__ void index_rows_equal_kernel(const uint64_t* __restrict__ held_hash,
+                                        const uint32_t* __restrict__ held_off,
+                                        const uint64_t* __restrict__ new_hash, const uint32_t* __restrict__ new_off,
+                                        uint32_t n, uint32_t* __restrict__ mismatch) {
+  bool diff = false;
+  for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x)
+    diff |= held_hash[r] != new_hash[r] || held_off[r] != new_off[r];
+  if (ballot(diff) != 0 && lane_id() == 0) atomicOr(mismatch, 1u);
 }
 
 struct IndexView {
@@ -723,11 +742,14 @@ using namespace kdb_lz4;
 struct ScanState {
   bool ready = false;
   uint64_t live = 0;
+  uint64_t closed_live = 0;              // of them, rows below the tail of a tail snapshot (kdb_live.h)
   uint32_t sort_steps = 0;
   uint64_t* d_live = nullptr;
   uint64_t* d_key_prefix = nullptr;
   std::vector<uint64_t> key_prefix;
 };
+
+struct kdb_snapshot;
 
 struct kdb_index {
   uint32_t hash_type = 1;
@@ -774,6 +796,10 @@ struct kdb_index {
   } tail;
   uint64_t tail_rows_parsed = 0;         // kdb_index_tail_stats
   uint64_t visible_rows() const { return nrows + tail.rows; }
+  // the open tail snapshots whose file has not been added closed
+  // (include/kdb_live.h): while there are any, the tail stays the file it is
+  std::vector<kdb_snapshot*> pins;
+  lp::Pin pin() const;
 };
 
 // The handle as of kdb_snapshot_create: its first `nrows` rows, `nfiles` file
@@ -783,8 +809,20 @@ struct kdb_snapshot {
   kdb_index* ix = nullptr;
   uint64_t nrows = 0;
   uint32_t nfiles = 0, nloaded = 0;
+  // kdb_snapshot_create_tail: nrows, nfiles and nloaded count the tail held
+  // then; closed_rows are the rows below it (= nrows without a tail)
+  uint64_t closed_rows = 0;
+  bool tail_included = false, pinned = false;
+  uint32_t tail_fileid = 0;
+  uint64_t tail_rows = 0;
   ScanState scan;
 };
+
+lp::Pin kdb_index::pin() const {
+  lp::Pin p{!pins.empty(), tail.fileid, tail.timestamp, tail.file_off, 0u};
+  for (const kdb_snapshot* s : pins) p.rows = std::max(p.rows, s->tail_rows);
+  return p;
+}
 
 namespace {
 
@@ -800,6 +838,7 @@ void scan_release(ScanState* sc) {
   sc->key_prefix.clear();
   sc->ready = false;
   sc->live = 0;
+  sc->closed_live = 0;
   sc->sort_steps = 0;
 }
 
@@ -855,6 +894,7 @@ struct AddTemps {
   uint64_t* d_row_hash = nullptr;        // set only where the row arrays had to grow
   uint32_t* d_row_off = nullptr;
   uint32_t* d_row_file = nullptr;
+  uint32_t* d_mismatch = nullptr;        // the pin's check
   ~AddTemps() {
     dfree(d_rec);
     dfree(d_pf);
@@ -873,6 +913,7 @@ struct AddTemps {
     dfree(d_row_hash);
     dfree(d_row_off);
     dfree(d_row_file);
+    dfree(d_mismatch);
   }
 };
 
@@ -883,7 +924,7 @@ hipError_t upload(hipStream_t st, T** d, const T* h, size_t n) {
   return hipSuccess;
 }
 
-enum class Refused { kNo, kTooMany, kOrder };
+enum class Refused { kNo, kTooMany, kOrder, kPinned };
 
 // Room for nrows rows beside the handle's row arrays, their first `keep` rows
 // copied: the arrays grow geometrically past the handle's capacity (a load
@@ -1053,6 +1094,41 @@ hipError_t index_add(kdb_index* ix, hipStream_t st, const uint64_t* file_off, co
   for (uint32_t f = 0; f < nadd; f++) file_status[f] = status[f];
   if (*refused != Refused::kNo) return hipSuccess;
 
+  // the pin (include/kdb_live.h): the tail's own file arrives first, where it
+  // lay, and its first rows are the rows the open tail snapshots stand on
+  const lp::Pin pin = ix->pin();
+  if (pin.pinned) {
+    lp::Request rq{lp::kAdd, false, false, !order.empty(), 0u, 0u, 0u, 0u};
+    if (rq.has_file) {
+      const uint32_t f = order[0];
+      rq.fileid = fileid[f];
+      rq.timestamp = rec[f].timestamp;
+      rq.file_off = file_off[f];
+      rq.num_entries = rec[f].num_entries;
+    }
+    // rows held and rows parsed lie in arrays of their own (a tail with rows forces grow_rows above)
+    if (!lp::allows(pin, rq) || (pin.rows && row_hash == ix->d_row_hash)) {
+      *refused = Refused::kPinned;
+      return hipSuccess;
+    }
+    if (pin.rows) {
+      uint32_t mismatch = 0;
+      const uint32_t n = (uint32_t)pin.rows;
+      KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_mismatch), 4u));
+      KDB_TRY(hipMemsetAsync(t.d_mismatch, 0, 4u, st));
+      hipLaunchKernelGGL(index_rows_equal_kernel, dim3(std::min<uint32_t>((n + 255u) / 256u, 2048u)), dim3(256), 0, st,
+                         ix->d_row_hash + nrows0, ix->d_row_off + nrows0, row_hash + nrows0, row_off + nrows0, n,
+                         t.d_mismatch);
+      KDB_TRY(hipGetLastError());
+      KDB_TRY(hipMemcpyAsync(&mismatch, t.d_mismatch, 4u, hipMemcpyDeviceToHost, st));
+      KDB_TRY(hipStreamSynchronize(st));
+      if (mismatch) {
+        *refused = Refused::kPinned;
+        return hipSuccess;
+      }
+    }
+  }
+
   // the scan orders by the file's rank; a file that did not load has no rows and no rank
   rank.resize(nf, 0xFFFFFFFFu);
   rank_file.resize(nf, 0u);
@@ -1107,6 +1183,8 @@ hipError_t index_add(kdb_index* ix, hipStream_t st, const uint64_t* file_off, co
   ix->add_done = true;
   ix->add_rows_parsed = rows_parsed;
   ix->tail = kdb_index::Tail{};          // the file that was open arrives closed, or has: its rows are numbered as they were
+  for (kdb_snapshot* s : ix->pins) s->pinned = false;      // checked above: from here on ordinary prefix snapshots
+  ix->pins.clear();
   *rows_added = rows_new;
   return hipSuccess;
 }
@@ -1322,6 +1400,8 @@ extern "C" int kdb_index_set_tail(kdb_index* ix, void* stream, const uint8_t* d_
   if (rows_added_out) *rows_added_out = 0;
   if (!ix || !f || (flags & ~KDB_INDEX_TAIL_REPARSE)) return KDB_PUT_EINVAL;
   const bool none = !f->open || f->incomplete;
+  if (!lp::allows(ix->pin(), lp::Request{lp::kSet, f->open != 0, f->incomplete != 0, false, f->fileid, 0u, 0u, 0u}))
+    return KDB_PUT_EINVAL;
   if (!none && (!d_files || ((ix->nfiles || ix->tail.held) && d_files != ix->d_files))) return KDB_PUT_EINVAL;
   const uint8_t* held = ix->d_files;
   if (!none) ix->d_files = d_files;      // a handle without files adopts the buffer
@@ -1339,7 +1419,7 @@ extern "C" int kdb_index_set_tail(kdb_index* ix, void* stream, const uint8_t* d_
 }
 
 extern "C" int kdb_index_drop_tail(kdb_index* ix, void* stream) {
-  if (!ix) return KDB_PUT_EINVAL;
+  if (!ix || !lp::allows(ix->pin(), lp::Request{lp::kDrop, false, false, false, 0u, 0u, 0u, 0u})) return KDB_PUT_EINVAL;
   bool refused = false;
   uint64_t gained = 0;
   return hip_code(index_tail(ix, (hipStream_t)stream, nullptr, false, &gained, &refused));
@@ -1481,12 +1561,15 @@ IndexView view_of(const kdb_index* ix, uint64_t nrows) {
 // into `sc`: all the handle's rows for its own scan (limited = false), a
 // snapshot's for the snapshot's.  The rank tables are the handle's current
 // ones: the ranks of loaded files do not move.
-hipError_t scan_prepare(const kdb_index* ix, ScanState* sc, uint64_t nrows, bool limited, hipStream_t st,
-                        int verify_header, uint64_t* stats_out) {
+// closed_rows <= nrows: the rows below a tail snapshot's tail; the live rows
+// among them are the exclusive sum of the flags read at that row.
+hipError_t scan_prepare(const kdb_index* ix, ScanState* sc, uint64_t nrows, uint64_t closed_rows, bool limited,
+                        hipStream_t st, int verify_header, uint64_t* stats_out) {
   ScanTemps t;
   const uint32_t n = (uint32_t)nrows;
   unsigned long long stats[3] = {0, 0, 0};
-  uint64_t live = 0;
+  uint64_t live = 0, closed_live = 0;
+  const bool below_tail = closed_rows < nrows;
   if (n) {
     KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_flag), (size_t)n * 4u));
     KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_klen), (size_t)n * 4u));
@@ -1505,6 +1588,7 @@ hipError_t scan_prepare(const kdb_index* ix, ScanState* sc, uint64_t nrows, bool
     KDB_TRY(hipGetLastError());
     KDB_TRY(launch_exclusive_scan(st, t.d_flag, n, t.d_pos, t.d_pos + n));
     KDB_TRY(hipMemcpyAsync(&live, t.d_pos + n, 8, hipMemcpyDeviceToHost, st));
+    if (below_tail) KDB_TRY(hipMemcpyAsync(&closed_live, t.d_pos + closed_rows, 8, hipMemcpyDeviceToHost, st));
     KDB_TRY(hipMemcpyAsync(stats, t.d_stats, sizeof stats, hipMemcpyDeviceToHost, st));
     KDB_TRY(hipStreamSynchronize(st));
     // iterator order is (file rank, offset): the compaction gives it unless
@@ -1537,6 +1621,7 @@ hipError_t scan_prepare(const kdb_index* ix, ScanState* sc, uint64_t nrows, bool
     }
   }
   sc->live = live;
+  sc->closed_live = below_tail ? closed_live : live;
   sc->key_prefix.assign((size_t)live + 1u, 0);
   KDB_TRY(hipMalloc(reinterpret_cast<void**>(&sc->d_key_prefix), ((size_t)live + 1u) * 8u));
   if (live) {
@@ -1554,11 +1639,11 @@ hipError_t scan_prepare(const kdb_index* ix, ScanState* sc, uint64_t nrows, bool
 }
 
 // kdb_index_scan_prepare and kdb_snapshot_scan_prepare.
-int scan_prepare_checked(const kdb_index* ix, ScanState* sc, uint64_t nrows, bool limited, void* stream,
-                         int verify_header, uint64_t* live, uint64_t* key_bytes, uint32_t* max_key_len) {
+int scan_prepare_checked(const kdb_index* ix, ScanState* sc, uint64_t nrows, uint64_t closed_rows, bool limited,
+                         void* stream, int verify_header, uint64_t* live, uint64_t* key_bytes, uint32_t* max_key_len) {
   scan_release(sc);
   uint64_t stats[3] = {0, 0, 0};
-  const hipError_t e = scan_prepare(ix, sc, nrows, limited, (hipStream_t)stream, verify_header, stats);
+  const hipError_t e = scan_prepare(ix, sc, nrows, closed_rows, limited, (hipStream_t)stream, verify_header, stats);
   if (e != hipSuccess) {
     scan_release(sc);
     return hip_code(e);
@@ -1613,7 +1698,8 @@ int scan_batch(const kdb_index* ix, const ScanState* sc, uint64_t nrows, void* s
 extern "C" int kdb_index_scan_prepare(kdb_index* ix, void* stream, int verify_header, uint64_t* live,
                                       uint64_t* key_bytes, uint32_t* max_key_len) {
   if (!ix || verify_header < 0 || verify_header > 1) return KDB_PUT_EINVAL;
-  return scan_prepare_checked(ix, &ix->scan, ix->visible_rows(), false, stream, verify_header, live, key_bytes, max_key_len);
+  return scan_prepare_checked(ix, &ix->scan, ix->visible_rows(), ix->visible_rows(), false, stream, verify_header,
+                              live, key_bytes, max_key_len);
 }
 
 extern "C" int kdb_index_scan_sort_steps(const kdb_index* ix, uint32_t* steps) {
@@ -1643,7 +1729,7 @@ extern "C" int kdb_snapshot_create(kdb_index* ix, kdb_snapshot** snap) {
   kdb_snapshot* p = new (std::nothrow) kdb_snapshot;
   if (!p) return KDB_PUT_EINVAL;
   p->ix = ix;
-  p->nrows = ix->nrows;
+  p->nrows = p->closed_rows = ix->nrows;
   p->nfiles = ix->nfiles;
   p->nloaded = ix->nloaded;
   ix->snapshots++;
@@ -1651,10 +1737,43 @@ extern "C" int kdb_snapshot_create(kdb_index* ix, kdb_snapshot** snap) {
   return KDB_PUT_OK;
 }
 
+// include/kdb_live.h: the same with the tail held; host bookkeeping alone
+extern "C" int kdb_snapshot_create_tail(kdb_index* ix, kdb_snapshot** snap) {
+  const int rc = kdb_snapshot_create(ix, snap);
+  if (rc != KDB_PUT_OK || !ix->tail.held) return rc;
+  kdb_snapshot* p = *snap;
+  p->nrows = ix->visible_rows();
+  p->nfiles = ix->nfiles + 1u;
+  p->nloaded = ix->nloaded + 1u;
+  p->tail_included = p->pinned = true;
+  p->tail_fileid = ix->tail.fileid;
+  p->tail_rows = ix->tail.rows;
+  ix->pins.push_back(p);
+  return KDB_PUT_OK;
+}
+
+extern "C" int kdb_snapshot_tail_stats(const kdb_snapshot* snap, uint32_t* included, uint32_t* fileid, uint64_t* rows,
+                                       uint32_t* pinned) {
+  if (!snap || !included) return KDB_PUT_EINVAL;
+  *included = snap->tail_included ? 1u : 0u;
+  if (fileid) *fileid = snap->tail_fileid;
+  if (rows) *rows = snap->tail_rows;
+  if (pinned) *pinned = snap->pinned ? 1u : 0u;
+  return KDB_PUT_OK;
+}
+
+extern "C" int kdb_snapshot_scan_closed_live(const kdb_snapshot* snap, uint64_t* n) {
+  if (!snap || !n || !snap->scan.ready) return KDB_PUT_EINVAL;
+  *n = snap->scan.closed_live;
+  return KDB_PUT_OK;
+}
+
 // Snapshot::Close (interface/snapshot.h:67-76)
 extern "C" int kdb_snapshot_release(kdb_snapshot* snap) {
   if (!snap) return KDB_PUT_EINVAL;
   scan_release(&snap->scan);
+  std::vector<kdb_snapshot*>& pins = snap->ix->pins;
+  pins.erase(std::remove(pins.begin(), pins.end(), snap), pins.end());
   snap->ix->snapshots--;
   delete snap;
   return KDB_PUT_OK;
@@ -1689,8 +1808,8 @@ extern "C" int kdb_snapshot_get_batch(const kdb_snapshot* snap, void* stream, co
 extern "C" int kdb_snapshot_scan_prepare(kdb_snapshot* snap, void* stream, int verify_header, uint64_t* live,
                                          uint64_t* key_bytes, uint32_t* max_key_len) {
   if (!snap || verify_header < 0 || verify_header > 1) return KDB_PUT_EINVAL;
-  return scan_prepare_checked(snap->ix, &snap->scan, snap->nrows, true, stream, verify_header, live, key_bytes,
-                              max_key_len);
+  return scan_prepare_checked(snap->ix, &snap->scan, snap->nrows, snap->closed_rows, true, stream, verify_header,
+                              live, key_bytes, max_key_len);
 }
 
 extern "C" int kdb_snapshot_scan_sort_steps(const kdb_snapshot* snap, uint32_t* steps) {

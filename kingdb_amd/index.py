@@ -31,6 +31,12 @@ set of closed HSTable files and the batched lookup in front of the decoder.
   .snapshot()             an HSTableSnapshot: get, locate, scan, items, compacted
                           and compacted_device as of now, while refresh() and
                           add_files() go on (kdb_snapshot_*; Database::NewSnapshot)
+  .snapshot(tail=True)    the same with the entries of the writer's open file
+                          in it, up to this moment (kdb_snapshot_create_tail):
+                          what the reference gets by flushing before a snapshot
+  .compact(carry_open=True)
+                          the compaction under a running writer: the open file
+                          moves into the new writer as it is (adopt_open)
   HSTableIndex(files, reserve=N) / .add_files(files)
                           the same for an uploaded index: new files go into
                           the N spare bytes behind the first ones
@@ -403,7 +409,7 @@ class _ReadPath:
                 b.free()
 
     def compact_copy(self, hstable_size: int = 32 << 20, batch: int = 65536, spare_bytes: int = 0,
-                     filetype: int = 2, lock: bool = True):
+                     filetype: int = 2, lock: bool = True, closed_only: bool = False):
         """The compaction of the reference (StorageEngine::Compaction, steps
         6-7): every live entry of the view copied as it is stored -- a fresh
         header, the key, the stored value bytes, no decode -- into files of
@@ -416,16 +422,26 @@ class _ReadPath:
         The window buffers are allocated once, for the largest window.
         filetype=1, lock=False writes the same windows as files of an ordinary
         database, timestamps counting with the ids: byte for byte the files of
-        compacted_device() where every live entry is self-contained."""
+        compacted_device() where every live entry is self-contained.
+        closed_only=True, on a snapshot(tail=True): only the live entries that
+        lie in the files closed when the snapshot was taken are copied (the
+        first kdb_snapshot_scan_closed_live entries of the list), and the
+        locked timestamp is those files'.  Liveness is still the snapshot's:
+        an entry the open file overwrites or deletes is not copied, and what
+        supersedes it stays in the open file, which HSTableIndex.compact(
+        carry_open=True) carries whole.  Without a tail it changes nothing."""
         from . import put
         batch = max(batch, 1)
         live, _, kmax = self._prepared(0, None)
+        if closed_only:
+            live = self._closed_live(live)
         windows = [(first, min(batch, live - first)) for first in range(0, live, batch)]
         big = 1 << 62
         ts = ctypes.c_uint64(0)
         ih, nfiles = self._view()
         _lib.check(lib().kdb_index_view_timestamp(ih, nfiles, ctypes.byref(ts)), "kdb_index_view_timestamp")
-        ts.value = max(ts.value, self._tail_timestamp())      # an index's tail is a file of its view
+        if not closed_only:
+            ts.value = max(ts.value, self._tail_timestamp())  # a view's tail is a file of that view
         nmax = max([n for _, n in windows], default=1)
         L = _Lookup(nmax, nmax * kmax)
         bufs = [L]
@@ -485,6 +501,10 @@ class _ReadPath:
     def _tail_timestamp(self) -> int:
         """The timestamp of the open file a view includes, 0 where it includes none."""
         return 0
+
+    def _closed_live(self, live: int) -> int:
+        """Of the `live` entries of the prepared scan, those in closed files: the list's first so many."""
+        return live
 
     def _compact_fail(self, L: _Lookup, n: int, decoded: bool) -> None:
         """The error compacted() raises, for the window's first value that does not decode."""
@@ -717,6 +737,11 @@ class HSTableIndex(_ReadPath):
         f = self._owner.open_file() if self._tail and self._owner is not None else None
         return f.timestamp if f is not None and f.fileid == self._tail["fileid"] else 0
 
+    def _closed_live(self, live: int) -> int:
+        if self._tail:
+            raise ValueError("closed_only: take a snapshot(tail=True) of an index that holds a tail")
+        return live
+
     def add_files(self, files: dict[str, bytes], stream: Stream | None = None) -> dict[str, int]:
         """Uploads `files` into the room HSTableIndex(..., reserve=) left behind
         the files the index holds, at 64-byte-aligned offsets, and adds them
@@ -770,7 +795,7 @@ class HSTableIndex(_ReadPath):
         return self.h, len(self.names)
 
     def compact(self, snapshot: "HSTableSnapshot | None" = None, hstable_size: int = 32 << 20, batch: int = 65536,
-                spare_bytes: int = 0):
+                spare_bytes: int = 0, carry_open: bool = False):
         """The compaction of a snapshot (one is taken if none is given) and
         the hand-over, StorageEngine::Compaction as a whole: returns (writer,
         index).  The writer holds the snapshot's live entries in compacted
@@ -783,7 +808,21 @@ class HSTableIndex(_ReadPath):
         arena's room for them.  This index, its writer and its arena are left
         untouched: closing and freeing them is where the memory of the
         overwritten and deleted entries is reclaimed.  ValueError where this
-        index's writer has a file open: close or cut it and refresh() first."""
+        index's writer has a file open: close or cut it and refresh() first.
+        carry_open=True compacts under the running writer instead
+        (storage_engine.h:604-1010), with no file cut: the snapshot (taken
+        here with tail=True after a refresh(tail=True) if none is given; a
+        tail snapshot may be given) is compacted with closed_only=True, every
+        closed file of this index that is not a loaded file of the snapshot is
+        adopted, and the writer's open file moves into the new writer as its
+        open file (adopt_open).  `index` has been refresh(tail=True)ed and
+        answers get and scan as this index does after refresh(tail=True),
+        except that a key whose newest entry is a delete in a compacted file
+        reads NOTFOUND.  Stop appending to this index's writer: the new one
+        goes on.  ValueError where the writer has closed files this index has
+        not refreshed: they would be lost."""
+        if carry_open:
+            return self._compact_carry(snapshot, hstable_size, batch, spare_bytes)
         if self._owner is not None and self._owner.open_bytes():
             raise ValueError("compact: the writer has an open file; close or cut it and refresh() first")
         if snapshot is not None and snapshot.index is not self:
@@ -805,17 +844,65 @@ class HSTableIndex(_ReadPath):
             w.free()
             raise
 
-    def snapshot(self) -> "HSTableSnapshot":
+    def _compact_carry(self, snapshot, hstable_size: int, batch: int, spare_bytes: int):
+        """compact(carry_open=True)."""
+        if snapshot is not None and snapshot.index is not self:
+            raise ValueError("compact: the snapshot is of another index")
+        owner = self._owner
+        if owner is not None:
+            held = {int(f) for f in self.fileid}
+            lost = ["%08x" % int(f) for f in owner.resident()[3] if int(f) not in held]
+            if lost:
+                raise ValueError(f"compact: the writer has closed files the index has not refreshed: {lost}")
+        snap = snapshot if snapshot is not None else self.snapshot(tail=owner is not None)
+        try:
+            f = owner.open_file() if owner is not None else None
+            loaded = {n for n in snap.names if snap.file_status[n] == 0}
+            rest = [i for i, n in enumerate(self.names) if n not in loaded]
+            need = sum((int(self.file_size[i]) + 63) & ~63 for i in rest) + 64
+            if f is not None:                # the open file so far and its staged rows
+                need += ((int(f.bytes) + 63) & ~63) + int(f.row_bytes) + 64
+            w = snap.compact_copy(hstable_size, batch, spare_bytes + need, closed_only=True)
+        finally:
+            if snapshot is None:
+                snap.close()
+        try:
+            first = max([int(x) for x in self.fileid] + ([int(f.fileid)] if f is not None else []), default=0) + 1
+            w.adopt(first, self.files.ptr, self.file_off[rest], self.file_size[rest], self.fileid[rest])
+            if f is not None:
+                w.adopt_open(owner)
+            ix = HSTableIndex.from_resident(w)
+        except Exception:
+            w.free()
+            raise
+        try:
+            ix.refresh(tail=True)
+        except Exception:
+            ix.close()
+            w.free()
+            raise
+        return w, ix
+
+    def snapshot(self, tail: bool = False) -> "HSTableSnapshot":
         """A read-only view of the index as it is now (kdb_snapshot_create;
         Database::NewSnapshot): its get, locate, scan, items and compaction go
         on answering over the files held at this moment while refresh() /
         add_files() add newer ones.  It copies nothing and costs no device
-        work.  Entries of the writer's still open file are not in a snapshot,
-        also where refresh(tail=True) has made them readable through the
-        index; close or cut the file and refresh() first to have them in it.
-        close() it, or use it as a context manager; close() of the index
-        closes the snapshots still open."""
-        return HSTableSnapshot(self)
+        work.  With tail=False entries of the writer's still open file are not
+        in it, also where refresh(tail=True) has made them readable through
+        the index.  With tail=True they are (kdb_snapshot_create_tail): an
+        index made by from_resident() is refresh(tail=True)ed first, and the
+        snapshot answers as an index made fresh over the closed files and the
+        open file closed as it is at this moment -- every put appended before
+        the call, with no file cut.  Until that file has closed and been
+        refresh()ed the index keeps it as its tail: drop_tail() and adds that
+        leave the file out are refused (HipError EINVAL).  `.tail` is None or
+        {"fileid", "rows"}; `names` lists the closed files, `entries` counts
+        the tail's rows too.  close() it, or use it as a context manager;
+        close() of the index closes the snapshots still open."""
+        if tail and self._owner is not None:
+            self.refresh(tail=True)
+        return HSTableSnapshot(self, tail)
 
     def close(self) -> None:
         for s in list(self._snapshots or ()):
@@ -843,7 +930,7 @@ class HSTableSnapshot(_ReadPath):
 
     _ABI = "kdb_snapshot"
 
-    def __init__(self, index: HSTableIndex):
+    def __init__(self, index: HSTableIndex, tail: bool = False):
         self.h = None
         self._scan = None
         self.index = index
@@ -851,7 +938,10 @@ class HSTableSnapshot(_ReadPath):
         self.names = list(index.names)
         self.file_status = dict(index.file_status)
         h = ctypes.c_void_p()
-        _lib.check(lib().kdb_snapshot_create(index.h, ctypes.byref(h)), "kdb_snapshot_create")
+        if tail:
+            _lib.check(lib().kdb_snapshot_create_tail(index.h, ctypes.byref(h)), "kdb_snapshot_create_tail")
+        else:
+            _lib.check(lib().kdb_snapshot_create(index.h, ctypes.byref(h)), "kdb_snapshot_create")
         self.h = h.value
         if index._snapshots is None:
             index._snapshots = []
@@ -860,7 +950,36 @@ class HSTableSnapshot(_ReadPath):
         _lib.check(lib().kdb_snapshot_entry_count(self.h, ctypes.byref(n)), "kdb_snapshot_entry_count")
         _lib.check(lib().kdb_snapshot_file_count(self.h, ctypes.byref(f)), "kdb_snapshot_file_count")
         self.entries = n.value
-        assert f.value == len(self.names)
+        included, fid, rows, _ = self.tail_stats()
+        self._tail = {"fileid": fid, "rows": rows} if included else None
+        self._tail_ts = index._tail_timestamp() if included else 0
+        assert f.value == len(self.names) + included
+
+    def tail_stats(self) -> tuple[int, int, int, int]:
+        """(included, fileid, rows, pinned): kdb_snapshot_tail_stats.  pinned
+        is 1 until the tail's file has closed and been added to the index."""
+        inc, fid, rows, pin = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+        _lib.check(lib().kdb_snapshot_tail_stats(self.h, ctypes.byref(inc), ctypes.byref(fid), ctypes.byref(rows),
+                                                 ctypes.byref(pin)), "kdb_snapshot_tail_stats")
+        return inc.value, fid.value, rows.value, pin.value
+
+    @property
+    def tail(self):
+        """None, or {"fileid", "rows"} of the open file as the snapshot took it (snapshot(tail=True))."""
+        return dict(self._tail) if self._tail else None
+
+    def closed_live(self) -> int:
+        """After a scan_prepare: the live entries in files closed when the
+        snapshot was taken, the first so many of the scan (kdb_snapshot_scan_closed_live)."""
+        n = ctypes.c_uint64(0)
+        _lib.check(lib().kdb_snapshot_scan_closed_live(self.h, ctypes.byref(n)), "kdb_snapshot_scan_closed_live")
+        return n.value
+
+    def _tail_timestamp(self) -> int:
+        return self._tail_ts
+
+    def _closed_live(self, live: int) -> int:
+        return self.closed_live()
 
     @property
     def files(self):

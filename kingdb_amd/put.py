@@ -407,6 +407,19 @@ class DeviceHSTableWriter:
                                                size.ctypes.data if n else None, fileid.ctypes.data if n else None, n),
                    "hstable_dev_adopt")
 
+    def adopt_open(self, src: "DeviceHSTableWriter", stream: Stream | None = None) -> None:
+        """The hand-over's last step (kdb_hstable_dev_adopt_open), after
+        adopt(): the file `src` has open becomes this writer's open file --
+        its bytes and staged rows copied device to device, its id, timestamp,
+        size, marks and row count taken over -- and closes here, after any
+        further appends, byte for byte as it would have closed in `src`.
+        Nothing happens where `src` has no file open.  `src` is not modified:
+        stop appending to it.  Refused (HipError EINVAL, both writers as
+        before): a file open here, another hstable_size or hash_type, a writer
+        of compacted files, an id this writer holds, bytes that do not fit."""
+        _lib.check(lib().kdb_hstable_dev_adopt_open(self.h, stream.ptr if stream else None,
+                                                    src.h if src is not None else None), "hstable_dev_adopt_open")
+
     def reset(self) -> None:
         """A fresh directory; the arena is kept."""
         _lib.check(lib().kdb_hstable_dev_reset(self.h), "hstable_dev_reset")
