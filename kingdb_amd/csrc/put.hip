@@ -17,7 +17,16 @@
 //     Order::IsLastPart (util/order.h:52-55) holds -- including the reference's
 //     corner cases (a first chunk that already looks "last" makes the entry
 //     self-contained and drops later chunks; a last chunk that does not look
-//     last leaves the first-part header and no offset array);
+//     last leaves the first-part header and no offset array).  The first
+//     order that looks last ends the value, with the size_value_compressed
+//     and CRC its own call handed on: every call with chunk + offset ==
+//     size_value hands them on (database.cc:149, 237, 257), which with empty
+//     chunks at the end is not only the final one, and a middle chunk that
+//     merely ends on size_value hands on neither.  Later orders are dropped
+//     (hstable_manager.h:787-799, 821-833).  Every call at offset 0 is a
+//     first part and starts the entry again; the unfinished entries the
+//     reference leaves for empty first chunks are not written, and a put
+//     with a refused call (status -1) leaves no bytes at all;
 //   * EntryHeader::EncodeTo (storage/format.h:224-255), crc32c::crc8
 //     (algorithm/crc32c.cc:439-475), XXH64 / MurmurHash3_x64_128 of the key
 //     (algorithm/hash.cc:9-23).
@@ -147,12 +156,23 @@ __global__ void put_policy_kernel(const uint8_t* __restrict__ op, const uint32_t
     bool enabled = true;
     uint64_t ts_offset = 0, comp_total = 0, off = 0, svc = 0, crc_bytes = 0;
     int32_t status = 0;
+    // HSTableManager over the orders as they are made.  Every call that is a
+    // last part (chunk + offset == size_value, database.cc:149) carries its
+    // size_value_compressed and the CRC (:237, 257); with empty chunks at the
+    // end several calls do.  The first order that looks like a last part
+    // (util/order.h:52-55) ends the value: pl is that part, its order carried
+    // pl_svc, and pl_crc tells whether it carried the CRC.  Every call at
+    // offset 0 is a first part and starts the entry again (pf): what came
+    // before it, empty chunks only, belongs to no entry here.
+    uint32_t pf = p0, pl = p1;
+    uint64_t pl_svc = 0;
+    bool pl_crc = false;
     for (uint32_t p = p0; p < p1; p++) {
       const uint64_t csz = chunk_len[p];
       const bool first = off == 0, last = csz + off == V;
       const bool do_comp = csz != 0;                                        // database.cc:155-158
       uint64_t o = off;
-      if (first) { enabled = true; ts_offset = 0; }                         // :160-163
+      if (first) { enabled = true; ts_offset = 0; pf = p; pl = p1; }        // :160-163
       if (!enabled) { o = ts_offset; ts_offset = o + csz; }                 // :165-172
       uint32_t m = kModeRaw;
       uint64_t fsz = csz;
@@ -175,8 +195,14 @@ __global__ void put_policy_kernel(const uint8_t* __restrict__ op, const uint32_t
           fsz = F;
         }
       }
-      if (do_comp && last) svc = enabled ? comp_total : (first ? ts_offset : o + csz);   // :237-248
+      uint64_t so = 0;                                                      // this call's size_value_compressed
+      if (do_comp && last) so = svc = enabled ? comp_total : (first ? ts_offset : o + csz);   // :237-248
       if (o + fsz > V + (do_comp ? pad : 0)) { status = -1; break; }        // :261-267
+      if (pl == p1 && ((so == 0 && o + fsz == V) || (so != 0 && o + fsz == so))) {   // util/order.h:52-55
+        pl = p;
+        pl_svc = so;
+        pl_crc = last;
+      }
       occ[p] = o;
       plen[p] = (uint32_t)fsz;
       mode[p] = m;
@@ -195,35 +221,30 @@ __global__ void put_policy_kernel(const uint8_t* __restrict__ op, const uint32_t
       big[1u + atomicAdd(big, 1u)] = v;          // its status is the wave kernel's to write
       continue;
     }
-    // HSTableManager over the orders: order i carries size_value_compressed and
-    // crc only if it is the last call (database.cc:237, 256).
+    // The entry the orders leave: parts pf .. pl are written, the rest dropped
+    // (before pf: empty; after pl: the key's location is forgotten once an
+    // order looked last, hstable_manager.h:787-799, 821-833).
     const uint32_t np = p1 - p0;
-    auto is_last = [&](uint32_t i) {                                        // util/order.h:52-55
-      const uint64_t so = (i == np - 1) ? svc : 0u;
-      const uint64_t end = occ[p0 + i] + plen[p0 + i];
-      return (so == 0 && end == V) || (so != 0 && end == so);
-    };
-    if (np == 0 || is_last(0)) {   // self-contained (WriteFirstPartOrSmallOrder)
+    if (np == 0 || pl == pf) {     // self-contained (WriteFirstPartOrSmallOrder)
       L.kind = 0;
       L.flags = kEntryFull;
       L.pad_hdr = 0;
-      L.svc_hdr = np == 1 ? svc : 0u;
-      L.hdr_crc_final = np == 1 ? 1u : 0u;
-      L.stored = np ? plen[p0] : 0u;
-      for (uint32_t i = 1; i < np; i++) mode[p0 + i] |= kDropped;
+      L.svc_hdr = pl_svc;
+      L.hdr_crc_final = pl_crc ? 1u : 0u;
+      L.stored = np ? plen[pf] : 0u;
+      for (uint32_t p = p0; p < p1; p++)
+        if (p != pf) mode[p] |= kDropped;
       entry_len[v] = header_len(L.flags, klen, V, 0) + klen + (uint32_t)L.stored;
     } else {
-      uint32_t t = np;   // first later order that looks like a last part
-      for (uint32_t i = 1; i < np; i++)
-        if (is_last(i)) { t = i; break; }
-      for (uint32_t i = (t < np ? t + 1 : np); i < np; i++) mode[p0 + i] |= kDropped;
-      const uint32_t wl = t < np ? t : np - 1;
-      L.stored = occ[p0 + wl] + plen[p0 + wl];
+      for (uint32_t p = p0; p < pf; p++) mode[p] |= kDropped;
+      for (uint32_t p = (pl < p1 ? pl + 1 : p1); p < p1; p++) mode[p] |= kDropped;
+      const uint32_t wl = pl < p1 ? pl : p1 - 1;
+      L.stored = occ[wl] + plen[wl];
       L.pad_hdr = pad;
-      if (t < np) {                                                          // hstable_manager.h:548-568
+      if (pl < p1) {                                                         // hstable_manager.h:548-568
         L.kind = 1;
-        L.svc_hdr = t == np - 1 ? svc : 0u;
-        L.hdr_crc_final = t == np - 1 ? 1u : 0u;
+        L.svc_hdr = pl_svc;
+        L.hdr_crc_final = pl_crc ? 1u : 0u;
         L.flags = kEntryFull | (L.svc_hdr > 0 ? (kUncompacted | kHasPadding) : 0u);
       } else {                                                               // first-part header stays
         L.kind = 2;

@@ -72,6 +72,9 @@ class Oracle:
                                       _u8p, ctypes.POINTER(c.c_uint64), ctypes.POINTER(c.c_uint32),
                                       ctypes.POINTER(c.c_uint64), ctypes.POINTER(c.c_uint32)]
         lib.orc_put_value.restype = c.c_int
+        lib.orc_put_value_calls.argtypes = lib.orc_put_value.argtypes + [
+            ctypes.POINTER(c.c_uint64), ctypes.POINTER(c.c_uint32), ctypes.POINTER(c.c_int32)]
+        lib.orc_put_value_calls.restype = c.c_int
         lib.orc_get_value.argtypes = [_u8p, c.c_uint64, c.c_uint64, c.c_uint64, c.c_uint32, c.c_uint32, c.c_int, _u8p,
                                       ctypes.POINTER(c.c_uint64)]
         lib.orc_get_value.restype = c.c_int
@@ -166,25 +169,34 @@ class Oracle:
                                     ctypes.byref(n))
         return st, out[: n.value].tobytes()
 
-    def put_value(self, key: bytes, value: bytes, chunks: list[int] | None = None) -> dict:
+    def put_value(self, key: bytes, value: bytes, chunks: list[int] | None = None, keep_going: bool = False) -> dict:
         """Database::PutPart over `chunks` (default: one chunk) of one value:
         {"parts": [(offset_chunk_compressed, chunk_final bytes)], "svc", "crc",
-        "stored": the value region (size_value + padding bytes)}; raises on IOError."""
+        "stored": the value region (size_value + padding bytes), "calls": per
+        call (size_value_compressed, crc32, rc) as handed to WriteBuffer::PutPart
+        -- svc and crc non-zero only where the call is a last part, rc -1 where
+        the call is refused}.  Raises on IOError unless keep_going: a refused
+        call then has rc -1 and an empty part, and the later calls go on as the
+        reference's do."""
         chunks = [len(value)] if chunks is None else list(chunks)
         assert sum(chunks) == len(value)
         n = len(chunks)
         cl = (ctypes.c_uint32 * max(n, 1))(*chunks)
         po = (ctypes.c_uint64 * max(n, 1))()
         pl = (ctypes.c_uint32 * max(n, 1))()
+        cs = (ctypes.c_uint64 * max(n, 1))()
+        cc = (ctypes.c_uint32 * max(n, 1))()
+        cr = (ctypes.c_int32 * max(n, 1))()
         svc, crc = ctypes.c_uint64(0), ctypes.c_uint32(0)
         stored = np.zeros(len(value) + self.padding(len(value)) + 64, np.uint8)
-        rc = self.lib.orc_put_value(_ptr(self._buf(key)), len(key), _ptr(self._buf(value)), len(value), cl, n,
-                                    _ptr(stored), po, pl, ctypes.byref(svc), ctypes.byref(crc))
-        if rc != 0:
+        rc = self.lib.orc_put_value_calls(_ptr(self._buf(key)), len(key), _ptr(self._buf(value)), len(value), cl, n,
+                                          _ptr(stored), po, pl, ctypes.byref(svc), ctypes.byref(crc), cs, cc, cr)
+        if rc != 0 or (not keep_going and any(cr[i] for i in range(n))):
             raise RuntimeError("PutPartValidSize IOError")
         parts = [(int(po[i]), stored[int(po[i]):int(po[i]) + int(pl[i])].tobytes()) for i in range(n)]
         return {"parts": parts, "svc": svc.value, "crc": crc.value,
-                "stored": stored[: len(value) + self.padding(len(value))].tobytes()}
+                "stored": stored[: len(value) + self.padding(len(value))].tobytes(),
+                "calls": [(int(cs[i]), int(cc[i]), int(cr[i])) for i in range(n)]}
 
 
 class PutState(ctypes.Structure):

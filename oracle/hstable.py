@@ -59,8 +59,20 @@ def hstable_header_block(orc, timestamp: int, hstable_size: int, hash_type: int,
 class Writer:
     """The reference's HSTable output for a sequential put stream."""
 
-    def __init__(self, orc, hstable_size: int = 32 << 20, hash_type: int = 1):
+    def __init__(self, orc, hstable_size: int = 32 << 20, hash_type: int = 1, batch_contract: bool = False):
+        """batch_contract: put() writes what kdb_put_entries_batch promises
+        (include/kdb_put.h), one entry or none per put, where
+        the reference -- and this writer by default -- leaves more:
+          * a put with a refused call (IOError, database.cc:261-266) leaves
+            nothing (status -1, no bytes); the reference keeps the orders of
+            the calls it accepted;
+          * a value whose first chunks are empty leaves the entry its last
+            call at offset 0 starts; the reference also leaves an unfinished
+            entry, header + key + zeros, for each such call before it."""
         self.orc = orc
+        self.batch_contract = batch_contract
+        self.refused: list[tuple[int, int]] = []   # (put, chunk) of every refused call
+        self.nput = 0
         self.size_block = hstable_size
         self.hash_type = hash_type
         self.files: dict[int, bytearray] = {}
@@ -73,7 +85,7 @@ class Writer:
         self.in_progress: dict[int, int] = {}
         self.location: dict[bytes, tuple[int, int]] = {}
         self.headersize: dict[bytes, int] = {}
-        self.log: list[list] = []   # per first-part order: [file id, offset, entry bytes, hash, kind]
+        self.log: list[list] = []   # per first-part order: [file id, offset, entry bytes, hash, kind, put]
 
     # ---- file management
     def hash(self, key: bytes) -> int:
@@ -133,6 +145,9 @@ class Writer:
         if not first:
             fid, off = self.location.get(key, (0, 0))
             if fid == 0 or (fid != self.cur and self.in_progress[fid] == 0):
+                if last:                                     # hstable_manager.h:821-833
+                    self.location.pop(key, None)
+                    self.headersize.pop(key, None)
                 return
             f = self.files[fid]
             hs = self.headersize[key]
@@ -164,8 +179,13 @@ class Writer:
         self.offarray[self.cur].append((hashed, off))
         self.offset_end += len(entry)
         self.log.append([self.cur, off, len(entry) if selfc else len(hdr) + len(key) + size_value + pad, hashed,
-                         0 if selfc else 2])
-        if not selfc:
+                         0 if selfc else 2, self.nput])
+        if selfc:
+            # a self-contained order ends whatever the key had in progress
+            # (hstable_manager.h:821-833): later parts find no location
+            self.location.pop(key, None)
+            self.headersize.pop(key, None)
+        else:
             self.location[key] = (self.cur, off)
             self.headersize[key] = len(hdr)
             self.padding_flag[self.cur] = True
@@ -174,11 +194,17 @@ class Writer:
 
     def put(self, key: bytes, value: bytes, chunks: list[int] | None = None) -> None:
         """Database::PutPart for each chunk of one value, then the orders it makes."""
-        pv = self.orc.put_value(key, value, chunks)
-        n = len(pv["parts"])
-        for i, (occ, final) in enumerate(pv["parts"]):
-            lastcall = i == n - 1
-            self._order(key, final, occ, len(value), pv["svc"] if lastcall else 0, pv["crc"] if lastcall else 0)
+        pv = self.orc.put_value(key, value, chunks, keep_going=True)
+        bad = [i for i, c in enumerate(pv["calls"]) if c[2] != 0]
+        self.refused += [(self.nput, i) for i in bad]
+        if not (bad and self.batch_contract):
+            # every call that is a last part carries size_value_compressed and the
+            # CRC (database.cc:149, 237, 257): with an empty chunk at the end, two do
+            start = max(i for i, (occ, _) in enumerate(pv["parts"]) if occ == 0) if self.batch_contract else 0
+            for (occ, final), (svc, crc, rc) in list(zip(pv["parts"], pv["calls"]))[start:]:
+                if rc == 0:
+                    self._order(key, final, occ, len(value), svc, crc)
+        self.nput += 1
 
     def put_calls(self, state, key: bytes, value: bytes, chunks: list[int] | None = None) -> None:
         """The same, one Database::PutPartValidSize call per chunk over a client
@@ -187,17 +213,31 @@ class Writer:
         import oracle
         chunks = [len(value)] if chunks is None else list(chunks)
         off = 0
-        for c in chunks:
+        for i, c in enumerate(chunks):
             r = oracle.put_part(self.orc, state, key, value[off:off + c], off, len(value))
             off += c
-            if r["rc"] != 0:
+            if r["mode"] == 3:
                 raise RuntimeError("PutPartValidSize IOError")
-            self._order(key, r["chunk_final"], r["occ"], len(value), r["svc"], r["crc"])
+            if r["rc"] != 0:                    # refused at database.cc:261-266: no order, the client goes on
+                self.refused.append((self.nput, i))
+            else:
+                self._order(key, r["chunk_final"], r["occ"], len(value), r["svc"], r["crc"])
+        self.nput += 1
 
     def dense(self):
         """The per-value view the GPU put path produces (kdb_put_entries_batch):
         (entry bytes, key hash, kind) per first-part order, in order; call after close()."""
-        return [(bytes(self.files[fid][off:off + ln]), h, k) for fid, off, ln, h, k in self.log]
+        return [(bytes(self.files[fid][off:off + ln]), h, k) for fid, off, ln, h, k, _ in self.log]
+
+    def dense_by_put(self):
+        """dense() grouped by put: one list per put() / put_calls() call.  A put
+        makes one first-part order, except that every call at offset 0 is one
+        (database.cc:148): a value whose first chunks are empty makes several,
+        and a put dropped as refused makes none."""
+        out = [[] for _ in range(self.nput)]
+        for fid, off, ln, h, k, p in self.log:
+            out[p].append((bytes(self.files[fid][off:off + ln]), h, k))
+        return out
 
     def close(self) -> dict[str, bytes]:
         """End of the batch and Database::Close: {"00000001": bytes, ...}."""

@@ -488,10 +488,19 @@ uint64_t orc_padding(uint64_t size_value) { return (size_value / 65536u + 1u) * 
  * chunk_final), as handed to WriteBuffer::PutPart.  Returns 0, or -1 where the
  * reference returns an IOError (compressor failure, or the write-outside-the-
  * allocated-memory check at database.cc:263-267).
+ *
+ * orc_put_value_calls is the same with what each call hands on: call_svc[i] and
+ * call_crc[i] are the size_value_compressed and crc32 arguments of call i
+ * (non-zero only where the call is a last part, chunk + offset == size_value,
+ * :149, 237, 257 -- with an empty chunk at the end that holds for two calls),
+ * call_rc[i] is 0 or -1 where the call is refused at :261-267.  A refused
+ * call queues no order and the client goes on with the next chunk: the value
+ * is not abandoned, and -1 is returned only for a compressor failure.
  */
-int orc_put_value(const uint8_t* key, uint32_t klen, const uint8_t* value, uint64_t size_value,
-                  const uint32_t* chunk_len, uint32_t nchunks, uint8_t* stored, uint64_t* part_off,
-                  uint32_t* part_len, uint64_t* svc, uint32_t* crc) {
+static int put_value_calls(const uint8_t* key, uint32_t klen, const uint8_t* value, uint64_t size_value,
+                           const uint32_t* chunk_len, uint32_t nchunks, uint8_t* stored, uint64_t* part_off,
+                           uint32_t* part_len, uint64_t* svc, uint32_t* crc, uint64_t* call_svc,
+                           uint32_t* call_crc, int32_t* call_rc) {
   int enabled = 1;
   uint64_t ts_offset = 0, comp_total = 0, off = 0;
   const uint64_t pad = orc_padding(size_value);
@@ -528,13 +537,27 @@ int orc_put_value(const uint8_t* key, uint32_t klen, const uint8_t* value, uint6
         fsz = (uint64_t)F;
       }
     }
+    uint64_t svc_i = 0;
     if (do_comp && last) {                                            /* :237-248 */
-      if (enabled) *svc = comp_total;
-      else if (first) *svc = ts_offset;
-      else *svc = occ + csz;
+      if (enabled) svc_i = comp_total;
+      else if (first) svc_i = ts_offset;
+      else svc_i = occ + csz;
+      *svc = svc_i;
     }
-    if (occ + fsz > size_value + (do_comp ? pad : 0)) { free(fr); return -1; }   /* :261-267 */
+    const int refused = occ + fsz > size_value + (do_comp ? pad : 0);   /* :261-267 */
+    /* (chunks sent in order are refused only where they are empty: a chunk that
+       was compressed or copied always leaves room for the rest, :197-209) */
+    if (refused && (!call_rc || fsz)) { free(fr); return -1; }
     if (first) c32 = orc_crc32c_extend(0, key, klen);                 /* :251-256 */
+    if (refused) {                /* an empty chunk past the value's room: nothing to stream or store */
+      call_svc[i] = svc_i;
+      call_crc[i] = last ? c32 : 0u;
+      call_rc[i] = -1;
+      part_off[i] = occ;
+      part_len[i] = 0;
+      off += csz;
+      continue;
+    }
     if (hdr_zero) {
       memset(stored + occ, 0, 8);
       memcpy(stored + occ + 8, chunk, csz);
@@ -544,11 +567,31 @@ int orc_put_value(const uint8_t* key, uint32_t klen, const uint8_t* value, uint6
     c32 = orc_crc32c_extend(c32, stored + occ, fsz);
     part_off[i] = occ;
     part_len[i] = (uint32_t)fsz;
+    if (call_rc) {
+      call_svc[i] = svc_i;
+      call_crc[i] = last ? c32 : 0u;                                  /* :257 */
+      call_rc[i] = 0;
+    }
     off += csz;
   }
   free(fr);
   *crc = c32;
   return 0;
+}
+
+int orc_put_value(const uint8_t* key, uint32_t klen, const uint8_t* value, uint64_t size_value,
+                  const uint32_t* chunk_len, uint32_t nchunks, uint8_t* stored, uint64_t* part_off,
+                  uint32_t* part_len, uint64_t* svc, uint32_t* crc) {
+  return put_value_calls(key, klen, value, size_value, chunk_len, nchunks, stored, part_off, part_len, svc, crc,
+                         NULL, NULL, NULL);
+}
+
+int orc_put_value_calls(const uint8_t* key, uint32_t klen, const uint8_t* value, uint64_t size_value,
+                        const uint32_t* chunk_len, uint32_t nchunks, uint8_t* stored, uint64_t* part_off,
+                        uint32_t* part_len, uint64_t* svc, uint32_t* crc, uint64_t* call_svc, uint32_t* call_crc,
+                        int32_t* call_rc) {
+  return put_value_calls(key, klen, value, size_value, chunk_len, nchunks, stored, part_off, part_len, svc, crc,
+                         call_svc, call_crc, call_rc);
 }
 
 /*

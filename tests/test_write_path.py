@@ -1,8 +1,12 @@
 """The write path around the codec.
 
-Pinned by tests/golden/hstable_streams.npz: put streams and the HSTable files
-the reference's own Database -> WriteBuffer -> HSTableManager wrote for them
-(tests/golden/make_golden_put.py, oracle/_ref/ref_db).
+Pinned by tests/golden/hstable_streams.npz and hstable_ragged.npz: put streams
+and the HSTable files the reference's own Database -> WriteBuffer ->
+HSTableManager wrote for them (tests/golden/make_golden_put.py and
+make_golden_ragged.py, oracle/_ref/ref_db).  The second file holds the ragged
+chunkings -- empty chunks, chunks dropped behind one that looks last, the
+disable rule on every position, refused calls -- that the first does not reach
+(tests/put_policy_model.py names the classes, test_put_branch_table counts them).
 
 CPU: the oracle restatement (oracle/hstable.py + lz4_oracle.c orc_put_value)
 reproduces every reference file byte for byte; the product's host-side HSTable
@@ -23,25 +27,31 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 from make_golden_put import decode_stream  # noqa: E402
 
 GOLD = os.path.join(ROOT, "tests", "golden", "hstable_streams.npz")
+GOLD_RAGGED = os.path.join(ROOT, "tests", "golden", "hstable_ragged.npz")
+REFUSED = {}            # stream name: the (record, chunk) pairs the reference refused
 
 
-def golden():
-    z = np.load(GOLD)
+def golden(path=GOLD):
+    z = np.load(path)
     out = {}
     for name in z["names"]:
         name = str(name)
         hs, ht, mps = (int(x) for x in z[f"{name}__opts"])
         files = {str(f): z[f"{name}__file_{f}"].tobytes() for f in z[f"{name}__files"]}
         out[name] = (decode_stream(z[f"{name}__stream"].tobytes()), hs, ht, files)
+        if f"{name}__refused" in z.files:
+            REFUSED[name] = [(int(a), int(b)) for a, b in z[f"{name}__refused"]]
     return out
 
 
-GOLDEN = golden()
+TIDY = golden()                          # hstable_streams.npz
+RAGGED = golden(GOLD_RAGGED)             # hstable_ragged.npz
+GOLDEN = {**TIDY, **RAGGED}
 
 
-def oracle_writer(orc, puts, hs, ht, batch=None):
+def oracle_writer(orc, puts, hs, ht, batch=None, batch_contract=False):
     from oracle import hstable
-    w = hstable.Writer(orc, hs, ht)
+    w = hstable.Writer(orc, hs, ht, batch_contract=batch_contract)
     step = batch or max(len(puts), 1)
     for i in range(0, len(puts), step):
         for k, v, ch in puts[i:i + step]:
@@ -65,6 +75,7 @@ def test_oracle_per_call_matches_reference_hstables(orc, name):
     w._flush(0, 0)
     got = w.close()
     assert got == files
+    assert w.refused == REFUSED.get(name, [])
 
 
 def test_oracle_per_call_matches_put_value(orc):
@@ -101,10 +112,11 @@ def test_oracle_per_call_matches_put_value(orc):
 @pytest.mark.parametrize("name", sorted(GOLDEN))
 def test_oracle_matches_reference_hstables(orc, name):
     puts, hs, ht, files = GOLDEN[name]
-    _, got = oracle_writer(orc, puts, hs, ht)
+    w, got = oracle_writer(orc, puts, hs, ht)
     assert list(got) == list(files)
     for f in files:
         assert got[f] == files[f], f
+    assert w.refused == REFUSED.get(name, [])
 
 
 @pytest.mark.parametrize("name", sorted(GOLDEN))
@@ -178,6 +190,64 @@ def test_host_hstable_writer_parallel_batches(orc, hs, batch):
         assert got[f] == files[f], f
 
 
+def test_put_branch_table(orc):
+    """Every branch of the put policy that tests/put_policy_model.py names is
+    reached by a put of hstable_ragged.npz, and hstable_streams.npz reaches
+    what it always did: a condition on the fixtures, not a measurement."""
+    import put_policy_model as model
+    classes = ["self_contained_one_chunk", "disable_one_chunk", "multipart_finished_svc", "disable_last_chunk",
+               "multipart_unfinished", "empty_value_one_chunk",
+               "self_contained_chunks_dropped", "early_last_chunks_dropped", "multipart_finished_svc0",
+               "disable_first_of_several", "disable_middle", "empty_chunk_first", "empty_chunk_middle",
+               "empty_chunk_last", "last_part_twice", "refused", "dropped_bytes_zero_filled"]
+    assert sorted(classes) == sorted(model.CLASSES)
+    tidy = {c: 0 for c in classes}
+    for puts, _, _, _ in TIDY.values():
+        for c, k in model.table(orc, puts).items():
+            tidy[c] += k
+    assert {c: k for c, k in tidy.items() if k} == {
+        "self_contained_one_chunk": 1643, "disable_one_chunk": 139, "multipart_finished_svc": 6,
+        "disable_last_chunk": 3, "multipart_unfinished": 3, "empty_value_one_chunk": 2}
+    ragged = {c: 0 for c in classes}
+    for puts, _, _, _ in RAGGED.values():
+        for c, k in model.table(orc, puts).items():
+            ragged[c] += k
+    print(ragged)
+    assert [c for c in classes if ragged[c] == 0] == []
+    # the streams are what their names say: the readable one has no refused call
+    # and no entry left unfinished, and the refused calls are the reference's
+    ok = model.table(orc, RAGGED["ragged_ok"][0])
+    assert ok["refused"] == 0 and ok["multipart_unfinished"] == 0 and ok["early_last_chunks_dropped"] == 0
+    assert REFUSED["ragged_ok"] == [] and len(REFUSED["ragged_odd"]) == model.table(
+        orc, RAGGED["ragged_odd"][0])["refused"] > 0
+
+
+@pytest.mark.parametrize("seed", [2, 3])
+def test_ragged_fuzz_oracle_equals_reference(orc, seed):
+    """The CPU twin of tests/test_gpu_put_ragged.py::test_fuzz_put_entries: the
+    reference itself (oracle/_ref/ref_db, refused calls reported and passed
+    over) writes the fuzz stream, and both oracle writers leave its files and
+    name its refused calls.  Skipped where the reference is not built."""
+    import oracle
+    import put_fuzz
+    from make_golden_put import REF_DB, encode_stream
+    from make_golden_ragged import run_ref_keep_going
+    from oracle import hstable
+    if not os.path.exists(REF_DB):
+        pytest.skip("oracle/_ref not built (no reference source here)")
+    assert seed in put_fuzz.SEEDS
+    puts = put_fuzz.stream(orc, seed)
+    files, refused = run_ref_keep_going(encode_stream(puts), 32 << 20, 1, 1 << 20, False)
+    w, got = oracle_writer(orc, puts, 32 << 20, 1)
+    assert got == files and w.refused == refused
+    w = hstable.Writer(orc, 32 << 20, 1)
+    st = oracle.PutState()
+    for k, v, ch in puts:
+        w.put_calls(st, k, v, ch)
+    w._flush(0, 0)
+    assert w.close() == files and w.refused == refused
+
+
 def test_db_options_bytes(orc):
     from kingdb_amd.put import db_options
     from oracle import hstable
@@ -220,7 +290,7 @@ def test_policy_disable_cases(orc):
 
 # ------------------------------------------------------------------ GPU
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", sorted(GOLDEN))
+@pytest.mark.parametrize("name", sorted(TIDY))      # (hstable_ragged.npz: tests/test_gpu_put_ragged.py)
 def test_gpu_put_entries_match_oracle(gpu, orc, name):
     from kingdb_amd.put import put_entries
     puts, hs, ht, files = GOLDEN[name]
@@ -238,7 +308,7 @@ def test_gpu_put_entries_match_oracle(gpu, orc, name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", sorted(GOLDEN))
+@pytest.mark.parametrize("name", sorted(TIDY))
 def test_gpu_write_path_matches_reference_files(gpu, name):
     from kingdb_amd.put import write_hstables
     puts, hs, ht, files = GOLDEN[name]
