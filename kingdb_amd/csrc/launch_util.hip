@@ -103,13 +103,10 @@ hipError_t work_counter_release(hipStream_t st, uint32_t* ctr) {
 // launches in flight never share rings.  The words are zeroed once, when the
 // pool is made: every launch has a generation of its own (never 0), and a word
 // of another generation reads as "nothing published".
-#ifndef KDB_LZ4_EMIT_HELPERS_DEFAULT
-#define KDB_LZ4_EMIT_HELPERS_DEFAULT 1
-#endif
-#ifndef KDB_LZ4_EMIT_RING_DEFAULT
-#define KDB_LZ4_EMIT_RING_DEFAULT 4   // (with five helpers: 7.31 ms against 7.35 at depth 2)
-#endif
 namespace {
+// what the environment knobs KDB_LZ4_EMIT_HELPERS and KDB_LZ4_EMIT_RING default to
+constexpr long kEmitHelpersDefault = 1;   // helpers on
+constexpr long kEmitRingDefault = 4;      // (with five helpers: 7.31 ms against 7.35 at depth 2)
 constexpr uint32_t kEmitSets = 8;
 struct EmitPool {
   uint8_t* base = nullptr;
@@ -133,7 +130,7 @@ long env_long(const char* name, long dflt) {
 hipError_t emit_scratch(hipStream_t st, uint32_t parse_waves, uint32_t ring_bytes, EmitScratch* es) {
   (void)st;
   *es = EmitScratch();
-  if (env_long("KDB_LZ4_EMIT_HELPERS", KDB_LZ4_EMIT_HELPERS_DEFAULT) == 0) return hipSuccess;
+  if (env_long("KDB_LZ4_EMIT_HELPERS", kEmitHelpersDefault) == 0) return hipSuccess;
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
@@ -178,7 +175,7 @@ hipError_t emit_scratch(hipStream_t st, uint32_t parse_waves, uint32_t ring_byte
   }
   uint32_t g = p->gen.fetch_add(1) + 1u;
   if (g == 0) g = p->gen.fetch_add(1) + 1u;
-  const long d = env_long("KDB_LZ4_EMIT_RING", KDB_LZ4_EMIT_RING_DEFAULT);
+  const long d = env_long("KDB_LZ4_EMIT_RING", kEmitRingDefault);
   uint8_t* set = p->base + (size_t)i * p->set_bytes;
   es->ctl = reinterpret_cast<uint64_t*>(set);
   es->ring = set + p->ctl_bytes;

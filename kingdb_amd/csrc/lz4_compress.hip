@@ -167,17 +167,6 @@ struct Table12T {
         : "=&v"(ol), "=&v"(oh)
         : "v"(al), "v"(ml), "v"(dl), "v"(s.hi), "v"(s.mh), "v"(dh)
         : "memory");
-#if KDB_ABL_DUP_XCHG
-    // attribution build (tools/gpurun/lds_attr.sh): the same two exchanges
-    // again as reads (mask 0, data 0), so their LDS bank conflicts count twice
-    uint32_t d0, d1;
-    asm volatile(
-        "ds_mskor_rtn_b32 %0, %2, %4, %4 offset:" KDB_STR(KDB_T12_LO) "\n\t"
-        "ds_mskor_rtn_b32 %1, %3, %4, %4 offset:" KDB_STR(KDB_T12_HI) "\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&v"(d0), "=&v"(d1) : "v"(h & ~3u), "v"(s.hi), "v"(0u) : "memory");
-    asm volatile("" ::"v"(d0), "v"(d1));
-#endif
     return (__builtin_amdgcn_ubfe(oh, s.sh, 4) << 8) | __builtin_amdgcn_ubfe(ol, sl, 8);
   }
   // v: a position < 4096; only lanes whose exchange was on (mh = their nibble mask)
@@ -336,9 +325,6 @@ struct Table24T {
 // the window's bytes serve the count, the literals and the next input words
 // (1 MiB parts: compress 22.3-22.7 -> 20.0 ms; untagged, it measured slower,
 // profiles/r04_d/r04_y2_ab_window_byu32.txt).
-#ifndef KDB_LZ4_WIDE_WINDOW
-#define KDB_LZ4_WIDE_WINDOW 1
-#endif
 // byU32 values with the tagged table read through an LDS ring (RingSrc)
 // instead of in place with the register window: 1 MiB parts compress
 // 20.0 -> 15.3 ms (profiles/r05/r05_rg*: a 4 KiB ring refilled 1 KiB at a
@@ -346,18 +332,7 @@ struct Table24T {
 // measured the same, 8 KiB or a 2 KiB front slower, and loading the next
 // chunk a refill ahead slower too -- its loads, in flight, then sat in front
 // of every other global access's in-order wait).
-#ifndef KDB_LZ4_WIDE_RING
-#define KDB_LZ4_WIDE_RING 1
-#endif
-#ifndef KDB_LZ4_RING_AHEAD
-#define KDB_LZ4_RING_AHEAD 0
-#endif
-#ifndef KDB_LZ4_RING_BYTES
-#define KDB_LZ4_RING_BYTES 4096u
-#endif
-#ifndef KDB_LZ4_RING_FRONT
-#define KDB_LZ4_RING_FRONT 512u
-#endif
+constexpr uint32_t kRingBytes = 4096u, kRingFront = 512u;
 
 // Value bytes staged in LDS (byte i at p[i]).  kUnclamped: a read outside the
 // value cannot fault (LDS), so the parse's reads whose result a lane mask
@@ -417,11 +392,11 @@ __device__ __forceinline__ uint4 funnel16(const uint4& a, const uint4& b, uint32
 // ~10 G1 sequences.  The ring holds positions [hi - kR, hi) at ring + (p mod
 // kR), with a kMirror-byte copy of its first bytes after its end so a 4-byte
 // read never wraps.
-template <uint32_t kRingBytes>
+template <uint32_t kBytes>
 struct RingSrcT {
   static constexpr bool kUnclamped = false;   // compress_block clamps (the fallback reads global memory)
   static constexpr bool kWindow = false;
-  static constexpr uint32_t kR = kRingBytes, kMirror = 64u, kChunk = 1024u, kFront = KDB_LZ4_RING_FRONT;
+  static constexpr uint32_t kR = kBytes, kMirror = 64u, kChunk = 1024u, kFront = kRingFront;
   typedef uint32_t __attribute__((aligned(1))) u32u;
   const uint8_t* g;
   uint32_t S;
@@ -460,11 +435,7 @@ struct RingSrcT {
   // Before a sequence's search from p: the ring filled to kFront past p (or
   // the value's end), 1 KiB at a time -- whole aligned 16-byte loads (an
   // aligned chunk never crosses a page, so reading around the value cannot
-  // fault), realigned in registers.  With KDB_LZ4_RING_AHEAD the next chunk's
-  // loads go out at the end of each refill and land in registers (na, nb)
-  // until the front needs them, so a refill rarely waits.
-  uint4 na, nb;
-  bool npend;
+  // fault), realigned in registers.
   // Only aligned chunks that hold a byte of the value are loaded (a chunk past
   // its end may lie past the allocation: zeros instead); the ring's bytes past
   // S are never used (compress_block clamps its reads into the value).
@@ -488,32 +459,16 @@ struct RingSrcT {
   __device__ __forceinline__ void step(uint32_t p) {
 #pragma unroll 1
     while (hi < S && p + kFront > hi) {
-#if KDB_LZ4_RING_AHEAD
-      if (npend) {
-        put(na, nb);
-        npend = false;
-        continue;
-      }
-#endif
       uint4 a, b;
       fetch(hi, a, b);
       put(a, b);
     }
-#if KDB_LZ4_RING_AHEAD
-    if (!npend && hi < S) {
-      fetch(hi, na, nb);
-      npend = true;
-    }
-#endif
   }
 };
 
-using RingSrc = RingSrcT<KDB_LZ4_RING_BYTES>;
+using RingSrc = RingSrcT<kRingBytes>;
 // the compact launch's ring (Table24T): 2 KiB, measured as fast as 4 KiB with the 16 KiB table
-#ifndef KDB_LZ4_COMPACT_RING
-#define KDB_LZ4_COMPACT_RING 2048u
-#endif
-using RingSrcC = RingSrcT<KDB_LZ4_COMPACT_RING>;
+using RingSrcC = RingSrcT<2048u>;
 
 // out chunk = bytes [sh, sh+16) of the 32 bytes (a, b); sh in 0..15 (uniform)
 __device__ __forceinline__ uint4 funnel16(const uint4& a, const uint4& b, uint32_t sh) {
@@ -892,35 +847,24 @@ __device__ __forceinline__ int compress_block(Src& src, uint32_t S, const Tab& t
     // its start is known (at the end of the sequence before), so the read
     // overlaps that sequence's byte store
     typename Src::Word seq0 = src.rd32_issue(clamp4(1u + lane));
-    // In-place values (HBM/L2): a 256-byte register window of the value from
-    // each match's start (one dword per lane, loaded with the count's bytes),
-    // from which the next sequence's input words and -- one sequence later --
-    // its literals come by ds_bpermute instead of two more global round trips
-    // per sequence (the chain is then: exchange, candidate word, count).
-    // A base of 2^31 marks "no window" (positions stay below 2^31).  byU16
-    // values only: for byU32 ones (1 MiB parts) it measured slower (8.47 ->
-    // 9.01 ms per 600 x 1 MiB).
-    constexpr bool kWin = !kFree && Src::kWindow && (!kWide || (KDB_LZ4_WIDE_WINDOW && Tab::kTagged));
-#ifndef KDB_LZ4_SEQ_WINDOW
-#define KDB_LZ4_SEQ_WINDOW 1
-#endif
-#if !KDB_LZ4_SEQ_WINDOW
-    uint32_t win = 0, wbase = 0x80000000u, pwin = 0, pbase = 0x80000000u;
-#endif
-#if KDB_LZ4_SEQ_WINDOW
-    // Round 4 (KDB_LZ4_SEQ_WINDOW, the default; 0 = the round-3 window
-    // above): one 256-byte window per sequence, loaded at the sequence's
-    // start from 64 bytes before its first search position -- an address
-    // known before the search -- so it lands with the candidate words, and
-    // the count's bytes, the literals and the next sequence's input words
-    // come out of it by ds_bpermute whenever they lie in it (near matches:
-    // all of G1's).  The sequence's chain is then one global round trip
-    // (candidate words and window together) instead of two (the candidate
-    // words, then the window's newest line, an HBM miss).  64 KiB x 10 486
-    // compress 3.71 -> 3.37 ms, mixed batch 5.34 -> 5.04 ms
-    // (profiles/r04_d/r04_u_ab_sequence_window.txt, digest-gated).
+    // In-place values (HBM/L2): one 256-byte register window of the value per
+    // sequence (one dword per lane), loaded at the sequence's start from 64
+    // bytes before its first search position -- an address known before the
+    // search -- so it lands with the candidate words, and the count's bytes,
+    // the literals and the next sequence's input words come out of it by
+    // ds_bpermute whenever they lie in it (near matches: all of G1's)
+    // instead of by more global round trips.  The sequence's chain is then
+    // one global round trip (candidate words and window together).  The
+    // round-3 window, removed, was loaded at each match's start with the
+    // count's bytes: two round trips (the candidate words, then the window's
+    // newest line, an HBM miss).  64 KiB x 10 486 compress 3.71 -> 3.37 ms,
+    // mixed batch 5.34 -> 5.04 ms (profiles/r04_d/r04_u_ab_sequence_window.txt,
+    // digest-gated).  A base of 2^31 marks "no window" (positions stay below
+    // 2^31).  byU16 values, and byU32 ones with a tagged table (the note
+    // before LdsSrc); for untagged byU32 values (1 MiB parts) it measured
+    // slower (8.47 -> 9.01 ms per 600 x 1 MiB).
+    constexpr bool kWin = !kFree && Src::kWindow && (!kWide || Tab::kTagged);
     uint32_t sw = 0, sbase = 0x80000000u;
-#endif
     // One sequence per call.  The sequence loop runs while anchor < lim_end:
     // mflimit + 1 (lz4.cc:597: a match that ends past mflimit leaves for the
     // last literals), or 0 once a search finds no match (the last literals)
@@ -952,18 +896,11 @@ __device__ __forceinline__ int compress_block(Src& src, uint32_t S, const Tab& t
     // literal runs are copied LDS -> HBM one sequence per wave-wide store.
     // The encoding's ~40 vector instructions per sequence leave the parse's
     // chain.  (lz4.cc:535-592: the same bytes.)
-#ifndef KDB_LZ4_BATCH_EMIT
-#define KDB_LZ4_BATCH_EMIT 1
-#endif
-    constexpr bool kBatch = KDB_LZ4_BATCH_EMIT && kBatchE && kFree && !kGuard && !kWide;
+    constexpr bool kBatch = kBatchE && kFree && !kGuard && !kWide;
     uint32_t rlm = 0, roff = 0;       // lane k: sequence k of the batch (lit | ml << 16, offset)
     uint32_t nseq = 0, banchor = 0;   // sequences recorded; the batch's first anchor
     auto flush_batch = [&]() {
-#if KDB_ABL_NO_EMIT   // (attribution build: the batch recorded but not encoded -- timing only, wrong output)
-      asm volatile("" ::"v"(rlm), "v"(roff));
-#else
       op = (int)flush_seqs(src, out_rsrc, rlm, roff, nseq, banchor, (uint32_t)op);
-#endif
       banchor = anchor;
       nseq = 0;
     };
@@ -998,7 +935,6 @@ __device__ __forceinline__ int compress_block(Src& src, uint32_t S, const Tab& t
         // harmless, clamped into the value only in HBM); the masks are
         // built while they are in flight
         const uint32_t ia = ip - 1u - lane, ra = ref - 1u - lane, ib = ip + kMinMatch + lane;
-#if KDB_LZ4_SEQ_WINDOW
         uint32_t a0, b0, a1, b1;
         uint32_t lim_w = lim;
         const uint32_t iw = ip - sbase, rw = ref - sbase;
@@ -1019,25 +955,11 @@ __device__ __forceinline__ int compress_block(Src& src, uint32_t S, const Tab& t
           a1 = src.u8(clamp1(ib));
           b1 = src.u8(clamp1(ref + kMinMatch + lane));
         }
-#else
-        const uint32_t lim_w = lim;
-        const uint32_t a0 = src.u8(clamp1(ia)), b0 = src.u8(clamp1(ra));
-        const uint32_t a1 = src.u8(clamp1(ib));
-        const uint32_t b1 = src.u8(clamp1(ref + kMinMatch + lane));
-#endif
         // in-place values: the restore (table writes) goes out behind the
         // count's reads (value bytes in HBM, no overlap), so their issue does
         // not wait behind it; it lands before the next sequence's exchange
         // all the same (measured: mixed batch compress -2 %; LDS-staged
         // values restore first, below the search: +1.7 % the other way)
-#if !KDB_LZ4_SEQ_WINDOW
-        if constexpr (kWin) {
-          pwin = win;
-          pbase = wbase;
-          wbase = ip;
-          win = src.rd32(min(ip + 4u * lane, last4));
-        }
-#endif
         if constexpr (!kFree) {
           if (ip - refk < pk - refk) tab.restore(slot, refk);
         }
@@ -1167,8 +1089,7 @@ __device__ __forceinline__ int compress_block(Src& src, uint32_t S, const Tab& t
           lb = src.u8(clamp1(seq_anchor + da));
         } else {
           // next input words: bytes ip_end - 2 + lane .. +3, at window offset
-          // ml + 2 + lane (ml before the catch-up); covered while ml <= 187
-#if KDB_LZ4_SEQ_WINDOW
+          // ip_end - 2 + lane - sbase; covered while ip_end - sbase <= 190
           const uint32_t pw = ip_end - sbase;
           if (pw <= 190u) {
             const uint32_t d = pw - 2u + lane;
@@ -1186,27 +1107,6 @@ __device__ __forceinline__ int compress_block(Src& src, uint32_t S, const Tab& t
           } else {
             lb = src.u8(clamp1(seq_anchor + da));
           }
-#else
-          const uint32_t mw = ip_end - wbase;               // 4 + ml
-          if (mw <= 191u) {
-            const uint32_t d = mw - 2u + lane;
-            const uint32_t w0 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((d >> 2) << 2), (int)win);
-            const uint32_t w1 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((d >> 2) + 1u) << 2), (int)win);
-            seq0 = typename Src::Word{__builtin_amdgcn_alignbyte(w1, w0, d & 3u)};
-          } else {
-            seq0 = src.rd32_issue(clamp4(ip_end - 2u + lane));
-          }
-          // literals [seq_anchor, seq_anchor + lit): in the previous match's
-          // window when they end inside it
-          const uint32_t lo = seq_anchor - pbase;
-          if (lo + lit <= 256u) {
-            const uint32_t o = lo + da;
-            const uint32_t w = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((o >> 2) << 2), (int)pwin);
-            lb = w >> ((o & 3u) << 3);
-          } else {
-            lb = src.u8(clamp1(seq_anchor + da));
-          }
-#endif
         }
         const uint32_t head = ((min(vlit, kRunMask) << 4) | min(vml, kMlMask)) | (remL << 8);
         const uint32_t tail = moff | (remM << 16);
@@ -1237,13 +1137,11 @@ __device__ __forceinline__ int compress_block(Src& src, uint32_t S, const Tab& t
       // cost more than it saved (64 KiB 6.51 -> 6.36 ms without it; 1 MiB
       // byU32 9.84 -> 10.71 ms without it, profiles/r02_e40_ab_touch.txt)
       if constexpr (kWide) src.step(anchor + 1u);
-#if KDB_LZ4_SEQ_WINDOW
       if constexpr (kWin) {
         const uint32_t cs = anchor + 1u - 3u * (decltype(lead_c)::value ? 1u : 0u);   // the first chunk's start
         sbase = cs >= 64u ? cs - 64u : 0u;
         sw = src.rd32(min(sbase + 4u * lane, last4));
       }
-#endif
       // ================= search (lz4.cc:494-527), 64 iterations per step
       // (the loop exits with the chunk that matched; a chunk that runs past
       // mflimit without a match goes to the last literals)
@@ -1275,14 +1173,6 @@ __device__ __forceinline__ int compress_block(Src& src, uint32_t S, const Tab& t
         } else {
           refk = tab.xchg(h, pk, valid, slot);
         }
-#if KDB_ABL_DUP_CAND
-        {  // attribution build: the candidate word read twice (opaque address, so both loads stay)
-          uint32_t r2 = refk;
-          asm volatile("" : "+v"(r2));
-          const uint32_t x = RD32(r2);
-          asm volatile("" ::"v"(x));
-        }
-#endif
         // the lanes whose reference matches (lz4.cc:527, 610-616), as a
         // compare straight into a lane mask (a ballot of a bool would be
         // materialised in a VGPR and compared again); byU32 adds the
@@ -1355,21 +1245,16 @@ __device__ __forceinline__ int compress_block(Src& src, uint32_t S, const Tab& t
       }
     }
     if constexpr (kBatch) {
-#if !KDB_ABL_NO_EMIT
       if constexpr (Hand::kOn) {
         // nothing flushed yet, so the whole value is this one batch: a helper
         // wave emits it, the last literals and the frame too
         if (op == 0 && banchor == 0u && hand->push(rlm, roff, S, anchor, nseq)) return kUnsupported;
       }
-#endif
       if (nseq) flush_batch();
     }
     if (kGuard && guard_fail) return 0;
   }
 
-#if KDB_ABL_NO_EMIT   // (attribution build: no last literals in the batched form -- timing only)
-  if constexpr (KDB_LZ4_BATCH_EMIT && kBatchE && Src::kUnclamped && !kGuard && !kWide) return unii((int)(S - anchor) + 1);
-#endif
   {  // the last literals (lz4.cc:625-637)
     const uint32_t run = S - anchor;
     if (kGuard && op + (int)run + 1 + (int)((run + 255u - kRunMask) / 255u) > cap) return 0;
@@ -1389,10 +1274,7 @@ constexpr uint32_t kSmallMax = 4096u;     // tagged table + register prefetch
 // Two instances of the parse in one kernel, picked per value (a runtime
 // choice per sequence inside one instance moved ~12 instructions per
 // sequence to the scalar unit: headline compress 8.48 -> 8.83 ms).
-#ifndef KDB_LZ4_BATCH_MIN
-#define KDB_LZ4_BATCH_MIN 512
-#endif
-constexpr uint32_t kBatchMin = KDB_LZ4_BATCH_MIN;
+constexpr uint32_t kBatchMin = 512u;
 constexpr uint32_t kMidLdsMax = 8192u;    // LDS-staged values up to here, in place above
 constexpr uint32_t kPrefetch = 4u;        // output chunks per lane: 4096 / 16 / 64
 
@@ -1434,12 +1316,10 @@ constexpr uint32_t kEmitDirect = 0, kEmitBatch = 1, kEmitPerValue = 2;
 // up with none of its ten waves' hand-offs (headline compress 8.01 ms
 // against the parent's 8.00), two with some (7.69), three 7.45, five
 // 7.31-7.35 ms (profiles/r07/r07_ab_helpers.txt).
-#ifndef KDB_LZ4_EMIT_NHELP
-#define KDB_LZ4_EMIT_NHELP 5
-#endif
+constexpr uint32_t kEmitHelpers = 5u;
 template <bool kSmall, uint32_t kEmit, uint32_t kWaves>
 constexpr uint32_t emit_helpers() {
-  return kSmall && kWaves > 1 && kEmit == kEmitBatch ? (uint32_t)KDB_LZ4_EMIT_NHELP : 0u;
+  return kSmall && kWaves > 1 && kEmit == kEmitBatch ? kEmitHelpers : 0u;
 }
 // kWaves > 1 (kSmall only): `smem` is this wave's 16 KiB region of a workgroup
 // of kWaves independent waves (lz4_compress_kernel), so the workgroup's
@@ -1568,13 +1448,7 @@ __device__ __forceinline__ void values_loop(
                           : compress_block<false, false, kEmit == kEmitBatch>(ls, S, tab, o + 8, (int)bound, (int)bound);
       if (Hand::kOn && r == kUnsupported) {
         // handed to a helper wave: it writes the block, the header, frame_len and the status
-      } else
-#if KDB_ABL_NO_EMIT   // (attribution build: the batched <= 4 KiB kernel writes no header and no status -- timing only)
-      if (kSmall && kEmit == kEmitBatch) {
-        asm volatile("" ::"s"(r));
-      } else
-#endif
-      if (r <= 0) {                              // compressor.cc:31-34
+      } else if (r <= 0) {                             // compressor.cc:31-34
         if (lane == 0) { ret[v] = -1; frame_len[v] = 0; }
       } else {
         const bool raw = (uint32_t)r > S;        // raw fallback (compressor.cc:40-48)
@@ -1634,13 +1508,8 @@ __global__ __launch_bounds__(64 * (kWaves + emit_helpers<kSmall, kEmit, kWaves>(
     // share the parse waves' SIMDs (their vector work is +5 % of the kernel's),
     // and a helper that loses an issue slot only finds its ring a little
     // fuller, while a parse wave that loses one lengthens its chain.
-    // -DKDB_LZ4_PARSE_PRIO=0: off (A/B); DESIGN.md section 9 has the numbers.
-#ifndef KDB_LZ4_PARSE_PRIO
-#define KDB_LZ4_PARSE_PRIO 1
-#endif
-#if KDB_LZ4_PARSE_PRIO
-    __builtin_amdgcn_s_setprio(KDB_LZ4_PARSE_PRIO);
-#endif
+    // DESIGN.md section 9 has the numbers against no priority.
+    __builtin_amdgcn_s_setprio(1);
   }
   // kSmall: a fixed LDS layout at LDS address 0 (the kernel's only LDS
   // array), so every LDS address is a constant offset (a dynamic
@@ -1677,6 +1546,10 @@ __global__ __launch_bounds__(64 * (kWaves + emit_helpers<kSmall, kEmit, kWaves>(
 // writes: 100 B Compress 3.87-4.13 -> 3.54-3.74 us); longer ones write the slot
 // directly (4 KiB through LDS measured 21.7 -> 23.3 us, profiles/r05/r05_sab4_*).
 constexpr uint32_t kSvcLdsOutMax = 256u;
+// This kernel shares compress_block<false, ...> instances with
+// lz4_compress_kernel, so which of those kernels this file instantiates shapes
+// its inlining: a change to that set changes this kernel's code and wants its
+// latency measured (profiles/refactor/service_latency.txt).
 __global__ __launch_bounds__(64) void lz4_compress_service_kernel(const SvcBox* ibox, SvcBox* obox, uint32_t gen, uint64_t idle_ticks,
                                                                   uint64_t life_ticks) {
   __shared__ __attribute__((aligned(16))) uint8_t smem_s[kTable12Bytes + kSmallMax];
@@ -1812,16 +1685,12 @@ __device__ __forceinline__ void big_values(
       };
       auto run_any = [&](uint32_t skip, int cap, int b) -> int {
         if constexpr (kCompact) {
-          RingSrcC rs{g, S, ring, 0u, {}, {}, false};
+          RingSrcC rs{g, S, ring, 0u};
           return run(rs, tabc, skip, cap, b);
         } else if constexpr (kWide) {
           if (tagged) {
-#if KDB_LZ4_WIDE_RING
-            RingSrc rs{g, S, ring, 0u, {}, {}, false};
+            RingSrc rs{g, S, ring, 0u};
             return run(rs, tabt, skip, cap, b);
-#else
-            return run(ws, tabt, skip, cap, b);
-#endif
           }
         }
         return run(ws, tab, skip, cap, b);
@@ -1873,7 +1742,7 @@ __global__ __launch_bounds__(64) void lz4_compress_big_kernel(
   if (prio) __builtin_amdgcn_s_setprio(2);
   __shared__ __attribute__((aligned(16))) uint32_t tab32[4096];
   // byU32 values' LDS ring (RingSrc); 16 + 4.06 KiB: 7 waves per CU (LDS)
-  __shared__ __attribute__((aligned(16))) uint8_t ring[kWide && KDB_LZ4_WIDE_RING ? RingSrc::kR + RingSrc::kMirror : 16u];
+  __shared__ __attribute__((aligned(16))) uint8_t ring[kWide ? RingSrc::kR + RingSrc::kMirror : 16u];
   big_values<kFrame, kWide>(tab32, ring, src, src_off, src_len, n, min_len, max_len, dst, dst_off, dst_cap, frame_len,
                             ret, work, batch);
 }
@@ -1907,7 +1776,7 @@ __global__ __launch_bounds__(64) void lz4_compress_big_compact_kernel(
 // in-place values' last rounds alone on the GPU).
 // kWaves: waves per workgroup, each in its own 16 KiB region (10 per CU
 // instead of 9, as lz4_compress_kernel).
-template <bool kFrame, uint32_t kWaves = 1>
+template <bool kFrame, uint32_t kWaves>
 __global__ __launch_bounds__(64 * kWaves) void lz4_compress_mixed_kernel(
     const uint8_t* __restrict__ src, const uint64_t* __restrict__ src_off,
     const uint32_t* __restrict__ src_len, uint32_t n, uint32_t big_min, uint32_t big_max,
@@ -1921,13 +1790,10 @@ __global__ __launch_bounds__(64 * kWaves) void lz4_compress_mixed_kernel(
   big_values<kFrame, false, false, kWaves>(smem32, nullptr, src, src_off, src_len, n, big_min, big_max, dst, dst_off,
                                            dst_cap, frame_len, ret, work_big, batch_big);
   value_sync<kWaves>();
-#ifndef KDB_LZ4_MIXED_EMIT
-#define KDB_LZ4_MIXED_EMIT kEmitPerValue
-#endif
   // the small pass: 100-byte and 4 KiB values together, each its own form
-  values_loop<kFrame, true, KDB_LZ4_MIXED_EMIT, kWaves>(reinterpret_cast<uint8_t*>(smem32), src, src_off, src_len, n, 0u,
-                                                        kSmallMax, dst, dst_off, dst_cap, frame_len, ret, work_small,
-                                                        batch_small, nq, 0u);
+  values_loop<kFrame, true, kEmitPerValue, kWaves>(reinterpret_cast<uint8_t*>(smem32), src, src_off, src_len, n, 0u,
+                                                   kSmallMax, dst, dst_off, dst_cap, frame_len, ret, work_small,
+                                                   batch_small, nq, 0u);
 }
 
 // Values per size class (len <= b0, <= b1, <= b2, above), so that a class
@@ -1964,7 +1830,7 @@ static hipError_t launch_one(hipStream_t st, size_t lds, const uint8_t* src, con
                              const uint64_t* dst_off, const uint32_t* dst_cap, uint32_t* frame_len,
                              int32_t* ret, const uint32_t* census = nullptr, uint32_t cls = 0,
                              uint32_t guide = 0) {
-  static_assert(W == 1 || Sm, "multi-wave workgroups: the <= 4 KiB class");
+  static_assert(Sm ? W > 1 : W == 1 && Em == kEmitBatch, "ten-wave workgroups for the <= 4 KiB class, one wave above");
   auto kern = lz4_compress_kernel<F, Sm, Em, W>;
   constexpr uint32_t H = emit_helpers<Sm, Em, W>();   // helper waves per workgroup (the batched ten-wave kernel)
   // see kOffLaneLds: the off lanes' first address (Table12 at kT12Lo in the
@@ -1987,18 +1853,10 @@ static hipError_t launch_one(hipStream_t st, size_t lds, const uint8_t* src, con
   const EmitHelp eh{es.ring, es.ctl, es.depth, es.gen, es.cap_ticks};
   const uint32_t batch = claim_batch(n, grid * W);
   // the rocprof (demangled) name
-  static const char* const names[2][2][3] = {
-      {{"lz4_compress_kernel<false, false, 0u, 1u>", "lz4_compress_kernel<false, false, 1u, 1u>",
-        "lz4_compress_kernel<false, false, 2u, 1u>"},
-       {"lz4_compress_kernel<false, true, 0u, 1u>", "lz4_compress_kernel<false, true, 1u, 1u>",
-        "lz4_compress_kernel<false, true, 2u, 1u>"}},
-      {{"lz4_compress_kernel<true, false, 0u, 1u>", "lz4_compress_kernel<true, false, 1u, 1u>",
-        "lz4_compress_kernel<true, false, 2u, 1u>"},
-       {"lz4_compress_kernel<true, true, 0u, 1u>", "lz4_compress_kernel<true, true, 1u, 1u>",
-        "lz4_compress_kernel<true, true, 2u, 1u>"}}};
   static const std::string multi = std::string("lz4_compress_kernel<") + (F ? "true" : "false") + ", true, " +
                                    std::to_string(Em) + "u, " + std::to_string(W) + "u>";
-  launch_note(W > 1 ? multi.c_str() : names[F][Sm][Em]);
+  launch_note(W > 1 ? multi.c_str()
+                    : F ? "lz4_compress_kernel<true, false, 1u, 1u>" : "lz4_compress_kernel<false, false, 1u, 1u>");
   hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * (W + H)), lds, st, src, src_off, src_len, n, min_len, in_cap, dst,
                      dst_off, dst_cap, frame_len, ret, work, batch, census, cls, work_queues(in_cap), guide, eh);
   e = hipGetLastError();
@@ -2032,14 +1890,11 @@ static hipError_t launch_big(hipStream_t st, const uint8_t* src, const uint64_t*
   return e != hipSuccess ? e : r;
 }
 
-#ifndef KDB_LZ4_MIXED_WAVES
-#define KDB_LZ4_MIXED_WAVES 10
-#endif
 template <bool F>
 static hipError_t launch_mixed(hipStream_t st, const uint8_t* src, const uint64_t* src_off, const uint32_t* src_len,
                                uint32_t n, uint32_t big_min, uint32_t big_max, uint8_t* dst, const uint64_t* dst_off,
                                const uint32_t* dst_cap, uint32_t* frame_len, int32_t* ret) {
-  constexpr uint32_t W = KDB_LZ4_MIXED_WAVES;
+  constexpr uint32_t W = 10;   // waves per workgroup, as the <= 4 KiB class launches (launch_compress)
   auto kern = lz4_compress_mixed_kernel<F, W>;
   const uint32_t grid = persistent_grid(reinterpret_cast<const void*>(kern), 0, n, W);
   uint32_t *wb = nullptr, *ws = nullptr;
@@ -2047,9 +1902,8 @@ static hipError_t launch_mixed(hipStream_t st, const uint8_t* src, const uint64_
   if (e == hipSuccess) e = launch_counter(st, n, grid * W, &ws);
   if (e == hipSuccess) {
     const uint32_t bb = wb ? claim_batch(n, grid * W) : 1u, bs = claim_batch(n, grid * W);
-    static_assert(W == 1 || W == 10, "the rocprof names below");
-    launch_note(W > 1 ? (F ? "lz4_compress_mixed_kernel<true, 10u>" : "lz4_compress_mixed_kernel<false, 10u>")
-                      : (F ? "lz4_compress_mixed_kernel<true, 1u>" : "lz4_compress_mixed_kernel<false, 1u>"));
+    static_assert(W == 10, "the rocprof names below");
+    launch_note(F ? "lz4_compress_mixed_kernel<true, 10u>" : "lz4_compress_mixed_kernel<false, 10u>");
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * W), 0, st, src, src_off, src_len, n, big_min, big_max, dst, dst_off,
                        dst_cap, frame_len, ret, wb, bb, ws, bs, work_queues(kSmallMax));
     e = hipGetLastError();
@@ -2108,18 +1962,17 @@ hipError_t launch_compress(bool frame, hipStream_t st, const uint8_t* src, const
   // The class launches stop at the first error, but the join of the forked
   // stream and the census slot's fence always follow: a caller that reuses
   // its buffers after an error must not race a kernel still queued on aux.
-  auto classes_run = [&]() -> hipError_t {
+  // (the body once per kFrame: frame_c is std::true_type or std::false_type)
+  auto classes_run = [&](auto frame_c) -> hipError_t {
+    constexpr bool F = decltype(frame_c)::value;
     hipError_t r = hipSuccess;
     if (combo) {
-      r = frame ? launch_mixed<true>(st, src, src_off, src_len, n, lo[2], hi[2], dst, dst_off, dst_cap, frame_len, ret)
-                : launch_mixed<false>(st, src, src_off, src_len, n, lo[2], hi[2], dst, dst_off, dst_cap, frame_len, ret);
+      r = launch_mixed<F>(st, src, src_off, src_len, n, lo[2], hi[2], dst, dst_off, dst_cap, frame_len, ret);
       if (r != hipSuccess) return r;
     }
     if (on[2] && !combo) {
-      r = frame ? launch_big<true, false>(aux, src, src_off, src_len, n, lo[2], hi[2], dst, dst_off, dst_cap, frame_len,
-                                          ret, census, 2)
-                : launch_big<false, false>(aux, src, src_off, src_len, n, lo[2], hi[2], dst, dst_off, dst_cap,
-                                           frame_len, ret, census, 2);
+      r = launch_big<F, false>(aux, src, src_off, src_len, n, lo[2], hi[2], dst, dst_off, dst_cap, frame_len, ret,
+                               census, 2);
       if (r != hipSuccess) return r;
     }
     if (on[3]) {
@@ -2127,52 +1980,26 @@ hipError_t launch_compress(bool frame, hipStream_t st, const uint8_t* src, const
       // test).  Host code takes no min() here: HIP's host min() on uint32_t is
       // the signed one (min(x, 0xFFFFFFFFu) == 0xFFFFFFFFu)
       const uint32_t top = max_len < hi[3] ? max_len : hi[3];
-      r = frame ? launch_big<true, true>(aux, src, src_off, src_len, n, lo[3], top, dst, dst_off, dst_cap,
-                                         frame_len, ret, census, 3)
-                : launch_big<false, true>(aux, src, src_off, src_len, n, lo[3], top, dst, dst_off, dst_cap,
-                                          frame_len, ret, census, 3);
+      r = launch_big<F, true>(aux, src, src_off, src_len, n, lo[3], top, dst, dst_off, dst_cap, frame_len, ret, census,
+                              3);
       if (r != hipSuccess) return r;
     }
     if (on[0] && !combo) {
       const size_t lds = 0;   // static LDS (compress_lds_bytes(kSmallMax) bytes)
       const uint32_t guide = claim_guide(max_len < kSmallMax ? max_len : kSmallMax);
+      // Ten waves per workgroup: one 160 KiB workgroup per CU, 10 values per
+      // CU instead of the 9 of one-wave workgroups (see lz4_compress_kernel).
+      // Five measured slower: two 80 KiB workgroups would make the same 10 per
+      // CU by the 1 280-byte step rule, but the hardware admitted one --
+      // compress 8.0 -> 15.1 ms (profiles/r06/r06_n_w5.txt)
+      constexpr uint32_t CW = 10;
       // batched emission when the launch may hold values of kBatchMin bytes
       // and more (a launch of short values only keeps the per-sequence form)
-      const bool bat = max_len >= kBatchMin;
-      // ten waves per workgroup (10 values per CU instead of 9, see
-      // lz4_compress_kernel); KDB_LZ4_WG10=0 (tuning builds): one
-#ifndef KDB_LZ4_WG10_DEFAULT
-#define KDB_LZ4_WG10_DEFAULT 1
-#endif
-      // waves per workgroup: 10 (one 160 KiB workgroup per CU), or 5 for A/B:
-      // two 80 KiB workgroups would make the same 10 per CU by the 1 280-byte
-      // step rule, but the hardware admitted one -- compress 8.0 -> 15.1 ms
-      // (profiles/r06/r06_n_w5.txt)
-#ifndef KDB_LZ4_CWAVES
-#define KDB_LZ4_CWAVES 10
-#endif
-      constexpr uint32_t CW = KDB_LZ4_CWAVES;
-      static_assert(CW == 5 || CW == 10, "16 KiB regions: 5 or 10 per 160 KiB");
-      static const bool wg10 = kdb_tune("KDB_LZ4_WG10", KDB_LZ4_WG10_DEFAULT) != 0;
-      if (wg10)
-        r = frame ? (bat ? launch_one<true, true, kEmitBatch, CW>(st, lds, src, src_off, src_len, n, 0u, kSmallMax, dst,
-                                                                  dst_off, dst_cap, frame_len, ret, census, 0, guide)
-                         : launch_one<true, true, kEmitDirect, CW>(st, lds, src, src_off, src_len, n, 0u, kSmallMax, dst,
-                                                                   dst_off, dst_cap, frame_len, ret, census, 0, guide))
-                  : (bat ? launch_one<false, true, kEmitBatch, CW>(st, lds, src, src_off, src_len, n, 0u, kSmallMax,
-                                                                   dst, dst_off, dst_cap, frame_len, ret, census, 0, guide)
-                         : launch_one<false, true, kEmitDirect, CW>(st, lds, src, src_off, src_len, n, 0u, kSmallMax,
-                                                                    dst, dst_off, dst_cap, frame_len, ret, census, 0,
-                                                                    guide));
-      else
-      r = frame ? (bat ? launch_one<true, true, kEmitBatch>(st, lds, src, src_off, src_len, n, 0u, kSmallMax, dst,
-                                                            dst_off, dst_cap, frame_len, ret, census, 0, guide)
-                       : launch_one<true, true, kEmitDirect>(st, lds, src, src_off, src_len, n, 0u, kSmallMax, dst,
-                                                             dst_off, dst_cap, frame_len, ret, census, 0, guide))
-                : (bat ? launch_one<false, true, kEmitBatch>(st, lds, src, src_off, src_len, n, 0u, kSmallMax, dst,
-                                                             dst_off, dst_cap, frame_len, ret, census, 0, guide)
-                       : launch_one<false, true, kEmitDirect>(st, lds, src, src_off, src_len, n, 0u, kSmallMax, dst,
-                                                              dst_off, dst_cap, frame_len, ret, census, 0, guide));
+      r = max_len >= kBatchMin
+              ? launch_one<F, true, kEmitBatch, CW>(st, lds, src, src_off, src_len, n, 0u, kSmallMax, dst, dst_off,
+                                                    dst_cap, frame_len, ret, census, 0, guide)
+              : launch_one<F, true, kEmitDirect, CW>(st, lds, src, src_off, src_len, n, 0u, kSmallMax, dst, dst_off,
+                                                     dst_cap, frame_len, ret, census, 0, guide);
       if (r != hipSuccess) return r;
     }
     // 4 KiB .. 8 KiB: the value staged in LDS (24 KiB with the table: 6 per CU);
@@ -2188,15 +2015,13 @@ hipError_t launch_compress(bool frame, hipStream_t st, const uint8_t* src, const
       // 1.4 ms even with no value of their own (1 MiB parts: compress 12.6 ->
       // 11.1 ms without the fork, profiles/r05/r05_nf_*)
       hipStream_t s1 = on[3] ? aux : st;
-      r = frame ? launch_one<true, false, kEmitBatch>(s1, lds, src, src_off, src_len, n, lo[1], top, dst, dst_off,
-                                                      dst_cap, frame_len, ret, census, 1, claim_guide(top))
-                : launch_one<false, false, kEmitBatch>(s1, lds, src, src_off, src_len, n, lo[1], top, dst, dst_off,
-                                                       dst_cap, frame_len, ret, census, 1, claim_guide(top));
+      r = launch_one<F, false, kEmitBatch>(s1, lds, src, src_off, src_len, n, lo[1], top, dst, dst_off, dst_cap,
+                                           frame_len, ret, census, 1, claim_guide(top));
     }
     return r;
   };
   e = fork ? fork_begin(st, &aux) : hipSuccess;
-  if (e == hipSuccess) e = classes_run();
+  if (e == hipSuccess) e = frame ? classes_run(std::true_type{}) : classes_run(std::false_type{});
   const hipError_t j = fork ? fork_end(st, aux) : hipSuccess;          // aux == st when fork_begin failed
   const hipError_t c = work_counter_release(st, census);                // its readers are all joined into st
   if (e == hipSuccess) e = j;

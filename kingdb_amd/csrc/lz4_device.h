@@ -220,7 +220,11 @@ __device__ __forceinline__ void flush_lds_to_global(uint8_t* g, const uint8_t* l
 // Diagnostic knobs for A/B experiments (class splits, ring sizes, grid caps,
 // stream fork): read from the environment only in a build with
 // -DKDB_LZ4_TUNING (tools/build_variants.sh <name>:-DKDB_LZ4_TUNING); the
-// shipped library always uses the defaults.
+// shipped library always uses the defaults.  Every knob picks between paths
+// that ordinary inputs reach too; -DKDB_LZ4_TUNING is the only build switch
+// of the LZ4 kernels (the decided experiments' switches, and the one-wave
+// <= 4 KiB compress kernels with their knob, are gone: DESIGN.md names the
+// last commit that has them).
 long kdb_tune(const char* name, long dflt);
 
 hipError_t work_counter(hipStream_t st, uint32_t** ctr);

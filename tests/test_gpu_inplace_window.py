@@ -1,5 +1,5 @@
 """The in-place compressor's per-sequence window (lz4_compress.hip,
-KDB_LZ4_SEQ_WINDOW): a sequence's count, literals and next input words come
+compress_block's kWin): a sequence's count, literals and next input words come
 out of a 256-byte window loaded at its start when they lie in it, and out of
 global memory when they do not.  These values put matches and literal runs on
 both sides of that window's edges -- sources 40..400 bytes back, literal runs

@@ -107,7 +107,7 @@ def main():
                     help="decompress told the batch's largest frame (not the slot bound)")
     ap.add_argument("--compress-only", action="store_true",
                     help="time the compress pass alone: no decompress, no digest, no round trip "
-                         "(attribution builds whose frames are wrong on purpose, e.g. -DKDB_ABL_NO_EMIT)")
+                         "(for a timing-only build whose frames are wrong on purpose)")
     a = ap.parse_args()
     from kingdb_amd import _lib
     _lib.load(os.path.abspath(a.so))
