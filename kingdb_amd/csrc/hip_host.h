@@ -31,4 +31,29 @@ inline uint32_t grid_for(uint64_t n, uint32_t per_block, uint32_t most) {
   return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + per_block - 1u) / per_block, most));
 }
 
+// The owner of one hipMalloc'd array of T: move-only, freed when it goes.
+template <class T>
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept { swap(o); }
+  DevBuf& operator=(DevBuf&& o) noexcept {   // the array held goes with o
+    swap(o);
+    return *this;
+  }
+  ~DevBuf() {
+    if (p_) (void)hipFree(p_);
+  }
+  // n elements; what it held is freed first
+  hipError_t alloc(size_t n) {
+    DevBuf().swap(*this);
+    return hipMalloc(reinterpret_cast<void**>(&p_), n * sizeof(T));
+  }
+  T* get() const { return p_; }
+  void swap(DevBuf& o) { std::swap(p_, o.p_); }
+
+ private:
+  T* p_ = nullptr;
+};
+
 }  // namespace kdb_lz4

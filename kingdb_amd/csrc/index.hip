@@ -37,6 +37,11 @@
 // index_parse_kernel<true> (csrc/index_rows.h) behind the closed files' rows,
 // only the bytes staged since the last call; the open file takes the next file
 // slot and rank, and hist / scan / fill run over all resident rows
+// Staged build and swap: load, add and tail are one transaction (Staged).  Its
+// steps build the per-file tables, the rows and the buckets beside the
+// handle's, every array owned by a DevBuf (hip_host.h); one commit() swaps in
+// what was staged once nothing can fail any more, and leaving before it frees
+// what was staged and leaves the handle as it was
 // Lookup (stream-ordered):
 //   index_get_kernel     wave per key: hash, bucket scan, candidates in
 //                        descending sequence number, header decode + checks
@@ -738,15 +743,46 @@ using namespace kdb_lz4;
 // A prepared scan (kdb_index_scan_prepare, kdb_snapshot_scan_prepare): the
 // live list, rank << 32 | offset in iterator order, and the exclusive sum of
 // the live keys' lengths (live + 1 entries, on the device for the emit and on
-// the host for the window checks).  The handle has one and every snapshot its own.
+// the host for the window checks).  The handle has one and every snapshot its
+// own; dropping one is assigning a fresh ScanState.
 struct ScanState {
   bool ready = false;
   uint64_t live = 0;
   uint64_t closed_live = 0;              // of them, rows below the tail of a tail snapshot (kdb_live.h)
   uint32_t sort_steps = 0;
-  uint64_t* d_live = nullptr;
-  uint64_t* d_key_prefix = nullptr;
   std::vector<uint64_t> key_prefix;
+  DevBuf<uint64_t> d_key_prefix, d_live;
+};
+
+// The closed files per slot, on the host: what kdb_index_add_files extends.
+// Mirrors of the device tables, the loaded files' timestamps (the order rule)
+// and the headers' file types.
+struct HostFiles {
+  std::vector<uint64_t> file_off, file_size, timestamp;
+  std::vector<uint32_t> fileid, filetype;
+  std::vector<int32_t> status;
+  std::vector<uint32_t> rank, rank_file;
+};
+
+// What a load, an add or a tail replaces, as one value.  The host vectors
+// stand before the device buffers, here and in every function that stages
+// arrays: members and locals go in reverse order, so the buffers are freed
+// first, and hipFree waits for the copies that read the vectors.
+// The buffers are declared last freed first, so that they go as they always
+// went -- file tables, buckets, rows -- and so do the temporaries of Staged and
+// of index_add: freed the other way round, a load and an add were measured
+// 0.2 to 0.3 ms slower (profiles/refactor/index_host_timing.txt).
+struct IndexArrays {
+  HostFiles host;
+  uint64_t nbuckets = 0, row_cap = 0;
+  DevBuf<uint32_t> d_row_file, d_row_off;
+  DevBuf<uint64_t> d_row_hash;           // the rows; they grow geometrically, row_cap has room
+  DevBuf<Slot> d_slots;
+  DevBuf<uint64_t> d_start;              // the buckets
+  DevBuf<uint32_t> d_rank_file;          // rank in (timestamp, fileid) order -> file slot
+  DevBuf<uint32_t> d_file_rank;          // and back
+  DevBuf<uint32_t> d_fileid;
+  DevBuf<uint64_t> d_file_size, d_file_off;
 };
 
 struct kdb_snapshot;
@@ -755,27 +791,9 @@ struct kdb_index {
   uint32_t hash_type = 1;
   const uint8_t* d_files = nullptr;      // the caller's
   uint32_t nfiles = 0;
-  uint64_t nrows = 0, nbuckets = 0;
-  uint64_t* d_file_off = nullptr;
-  uint64_t* d_file_size = nullptr;
-  uint32_t* d_fileid = nullptr;
-  uint64_t* d_start = nullptr;
-  Slot* d_slots = nullptr;
-  uint64_t* d_row_hash = nullptr;
-  uint32_t* d_row_off = nullptr;
-  uint32_t* d_row_file = nullptr;
-  uint32_t* d_file_rank = nullptr;       // file slot -> rank in (timestamp, fileid) order
-  uint32_t* d_rank_file = nullptr;       // and back
-  std::vector<uint32_t> fileid;
-  // what kdb_index_add_files extends: host copies of the per-file arrays, the
-  // loaded files' timestamps (the order rule), and the rows the row arrays
-  // have room for (they grow geometrically)
-  std::vector<uint64_t> file_off, file_size, timestamp;
-  std::vector<int32_t> status;
-  std::vector<uint32_t> filetype;        // the headers' file types, per slot
-  std::vector<uint32_t> rank, rank_file;
+  uint64_t nrows = 0;
+  IndexArrays a;
   uint32_t nloaded = 0;                  // files of status 0: the ranks in use
-  uint64_t row_cap = 0;
   // kdb_index_add_stats
   bool add_done = false;
   uint64_t add_rows_parsed = 0;
@@ -786,8 +804,8 @@ struct kdb_index {
   // the tail (include/kdb_index_tail.h): the rows of the writer's open file,
   // rows [nrows, nrows + tail.rows) of the row arrays and of the buckets, the
   // file in slot nfiles and rank nloaded of the device arrays.  nrows, nfiles,
-  // nloaded and the host vectors above count the closed files alone: they are
-  // what an add extends and a snapshot takes.
+  // nloaded and a.host count the closed files alone: they are what an add
+  // extends and a snapshot takes.
   struct Tail {
     bool held = false;
     uint32_t fileid = 0;
@@ -826,193 +844,212 @@ lp::Pin kdb_index::pin() const {
 
 namespace {
 
-template <class T>
-void dfree(T*& p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
-void scan_release(ScanState* sc) {
-  dfree(sc->d_live);
-  dfree(sc->d_key_prefix);
-  sc->key_prefix.clear();
-  sc->ready = false;
-  sc->live = 0;
-  sc->closed_live = 0;
-  sc->sort_steps = 0;
-}
-
 void index_release(kdb_index* ix) {
-  scan_release(&ix->scan);
-  dfree(ix->d_file_rank);
-  dfree(ix->d_rank_file);
-  dfree(ix->d_file_off);
-  dfree(ix->d_file_size);
-  dfree(ix->d_fileid);
-  dfree(ix->d_start);
-  dfree(ix->d_slots);
-  dfree(ix->d_row_hash);
-  dfree(ix->d_row_off);
-  dfree(ix->d_row_file);
+  ix->scan = ScanState{};
+  ix->a = IndexArrays{};
   ix->d_files = nullptr;
-  ix->nfiles = 0;
-  ix->nrows = ix->nbuckets = 0;
-  ix->fileid.clear();
-  ix->file_off.clear();
-  ix->file_size.clear();
-  ix->timestamp.clear();
-  ix->filetype.clear();
-  ix->status.clear();
-  ix->rank.clear();
-  ix->rank_file.clear();
-  ix->nloaded = 0;
-  ix->row_cap = 0;
+  ix->nfiles = ix->nloaded = 0;
+  ix->nrows = 0;
   ix->add_done = false;
   ix->add_rows_parsed = 0;
   ix->tail = kdb_index::Tail{};
   ix->tail_rows_parsed = 0;
 }
 
-// Temporaries of one add, and what it builds beside the handle: the new
-// arrays are swapped into the handle at the very end, so after a successful
-// add these hold what the handle held before.  All freed on every way out.
-struct AddTemps {
-  FileRec* d_rec = nullptr;
-  ParseFile* d_pf = nullptr;
-  uint32_t* d_tile_file = nullptr;
-  uint32_t* d_tile_count = nullptr;
-  uint64_t* d_tile_prefix = nullptr;
-  uint32_t* d_malformed = nullptr;
-  uint32_t* d_count = nullptr;
-  uint64_t* d_file_off = nullptr;
-  uint64_t* d_file_size = nullptr;
-  uint32_t* d_fileid = nullptr;
-  uint32_t* d_file_rank = nullptr;
-  uint32_t* d_rank_file = nullptr;
-  uint64_t* d_start = nullptr;
-  Slot* d_slots = nullptr;
-  uint64_t* d_row_hash = nullptr;        // set only where the row arrays had to grow
-  uint32_t* d_row_off = nullptr;
-  uint32_t* d_row_file = nullptr;
-  uint32_t* d_mismatch = nullptr;        // the pin's check
-  ~AddTemps() {
-    dfree(d_rec);
-    dfree(d_pf);
-    dfree(d_tile_file);
-    dfree(d_tile_count);
-    dfree(d_tile_prefix);
-    dfree(d_malformed);
-    dfree(d_count);
-    dfree(d_file_off);
-    dfree(d_file_size);
-    dfree(d_fileid);
-    dfree(d_file_rank);
-    dfree(d_rank_file);
-    dfree(d_start);
-    dfree(d_slots);
-    dfree(d_row_hash);
-    dfree(d_row_off);
-    dfree(d_row_file);
-    dfree(d_mismatch);
-  }
-};
-
 template <class T>
-hipError_t upload(hipStream_t st, T** d, const T* h, size_t n) {
-  KDB_TRY(hipMalloc(reinterpret_cast<void**>(d), std::max<size_t>(n, 1) * sizeof(T)));
-  if (n) KDB_TRY(hipMemcpyAsync(*d, h, n * sizeof(T), hipMemcpyHostToDevice, st));
+hipError_t upload(hipStream_t st, DevBuf<T>* d, const T* h, size_t n) {
+  KDB_TRY(d->alloc(std::max<size_t>(n, 1)));
+  if (n) KDB_TRY(hipMemcpyAsync(d->get(), h, n * sizeof(T), hipMemcpyHostToDevice, st));
   return hipSuccess;
 }
 
 enum class Refused { kNo, kTooMany, kOrder, kPinned };
 
-// Room for nrows rows beside the handle's row arrays, their first `keep` rows
-// copied: the arrays grow geometrically past the handle's capacity (a load
-// sizes them exactly) and the handle keeps its own until the swap.
-hipError_t grow_rows(const kdb_index* ix, hipStream_t st, uint64_t nrows, uint64_t keep, AddTemps* t,
-                     uint64_t* row_cap) {
-  const uint64_t cap = nrows > ix->row_cap ? std::max(nrows, std::min(2u * ix->row_cap, kMaxRows)) : ix->row_cap;
-  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t->d_row_hash), cap * 8u));
-  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t->d_row_off), cap * 4u));
-  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t->d_row_file), cap * 4u));
-  if (keep) {
-    KDB_TRY(hipMemcpyAsync(t->d_row_hash, ix->d_row_hash, keep * 8u, hipMemcpyDeviceToDevice, st));
-    KDB_TRY(hipMemcpyAsync(t->d_row_off, ix->d_row_off, keep * 4u, hipMemcpyDeviceToDevice, st));
-    KDB_TRY(hipMemcpyAsync(t->d_row_file, ix->d_row_file, keep * 4u, hipMemcpyDeviceToDevice, st));
-  }
-  *row_cap = cap;
-  return hipSuccess;
+// The order rule of an add and, ahead of time, of a tail: see index_rows.h.
+bool sorts_after_loaded(const kdb_index* ix, uint64_t timestamp, uint32_t fileid) {
+  const HostFiles& h = ix->a.host;
+  return ir::sorts_after_loaded(h.timestamp.data(), h.fileid.data(), h.status.data(), ix->nfiles, timestamp, fileid);
 }
 
-// The buckets over rows [0, nrows) of the given row arrays, into t->d_start
-// and t->d_slots: built from all resident rows, as a load builds them, whether
-// B doubles or stays -- moving the old slots and placing only the new rows was
-// measured and not kept.  The add and the tail share
-// this.  No rows: no buckets, *B = 0 (the lookup asks the row count first).
-hipError_t build_buckets(hipStream_t st, const uint64_t* row_hash, const uint32_t* row_off, const uint32_t* row_file,
-                         uint64_t nrows, AddTemps* t, uint64_t* B_out) {
-  *B_out = 0;
-  if (nrows == 0) return hipSuccess;
-  uint64_t B = 2;
-  while (B < 2u * nrows) B <<= 1;
-  const uint32_t n = (uint32_t)nrows;
-  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t->d_start), (B + 1u) * 8u));
-  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t->d_slots), nrows * sizeof(Slot)));
-  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t->d_count), B * 4u));
-  KDB_TRY(hipMemsetAsync(t->d_count, 0, B * 4u, st));
-  const uint32_t g = std::min<uint32_t>((n + 255u) / 256u, 2048u);
-  hipLaunchKernelGGL(index_hist_kernel, dim3(g), dim3(256), 0, st, row_hash, n, B - 1u, t->d_count);
-  KDB_TRY(hipGetLastError());
-  KDB_TRY(launch_exclusive_scan(st, t->d_count, (uint32_t)B, t->d_start, t->d_start + B));
-  hipLaunchKernelGGL(index_fill_kernel, dim3(g), dim3(256), 0, st, row_hash, row_off, row_file, n, B - 1u,
-                     t->d_start, t->d_count, t->d_slots);
-  KDB_TRY(hipGetLastError());
-  *B_out = B;
-  return hipSuccess;
-}
+// One load, add or tail: everything is built here, beside the handle, by the
+// steps below, and commit() swaps it in at the very end.  A buffer no step
+// filled stays null and means "keep the handle's".  Leaving without commit()
+// frees what was staged and leaves the handle as it was; after commit() this
+// holds what the handle held before, and frees that.
+struct Staged {
+  const kdb_index* ix;
+  const bool closed_files;               // an add: a.host goes to the handle.  A tail's file is in the device tables only
+  IndexArrays a;                         // host: the handle's, copied; the steps extend them
+  bool rebuilt = false;                  // build_buckets ran: a.d_start, a.d_slots and a.nbuckets count, null or not
+  // temporaries of the steps
+  DevBuf<uint32_t> d_count, d_malformed;
+  DevBuf<uint64_t> d_tile_prefix;
+  DevBuf<uint32_t> d_tile_count, d_tile_file;
+  DevBuf<ParseFile> d_pf;
+
+  // (a tail uploads from five of the eight vectors; all are copied, a few words a file)
+  Staged(const kdb_index* from, bool closed) : ix(from), closed_files(closed) { a.host = from->a.host; }
+
+  // the row arrays the parse writes and the buckets are built over
+  uint64_t* row_hash() const { return a.d_row_hash.get() ? a.d_row_hash.get() : ix->a.d_row_hash.get(); }
+  uint32_t* row_off() const { return a.d_row_hash.get() ? a.d_row_off.get() : ix->a.d_row_off.get(); }
+  uint32_t* row_file() const { return a.d_row_hash.get() ? a.d_row_file.get() : ix->a.d_row_file.get(); }
+  uint64_t row_cap() const { return a.d_row_hash.get() ? a.row_cap : ix->a.row_cap; }
+
+  void append_file(uint64_t off, uint64_t size, uint32_t id) {
+    a.host.file_off.push_back(off);
+    a.host.file_size.push_back(size);
+    a.host.fileid.push_back(id);
+  }
+
+  hipError_t upload_file_tables(hipStream_t st, uint32_t nf) {
+    KDB_TRY(upload(st, &a.d_file_off, a.host.file_off.data(), nf));
+    KDB_TRY(upload(st, &a.d_file_size, a.host.file_size.data(), nf));
+    return upload(st, &a.d_fileid, a.host.fileid.data(), nf);
+  }
+
+  // An add knows its ranks only after its parse.  The tail knows them at once
+  // and uploads them with the file tables: after the parse's synchronise the
+  // same two copies cost a refresh 0.1 ms (profiles/refactor/index_host_timing.txt)
+  hipError_t upload_ranks(hipStream_t st, uint32_t nf) {
+    KDB_TRY(upload(st, &a.d_file_rank, a.host.rank.data(), nf));
+    return upload(st, &a.d_rank_file, a.host.rank_file.data(), nf);
+  }
+
+  // Room for nrows rows beside the handle's row arrays, their first `keep`
+  // rows copied: the arrays grow geometrically past the handle's capacity (a
+  // load sizes them exactly) and the handle keeps its own until the swap.
+  hipError_t grow_rows(hipStream_t st, uint64_t nrows, uint64_t keep) {
+    const uint64_t held = ix->a.row_cap;
+    const uint64_t cap = nrows > held ? std::max(nrows, std::min(2u * held, kMaxRows)) : held;
+    KDB_TRY(a.d_row_hash.alloc(cap));
+    KDB_TRY(a.d_row_off.alloc(cap));
+    KDB_TRY(a.d_row_file.alloc(cap));
+    if (keep) {
+      KDB_TRY(hipMemcpyAsync(a.d_row_hash.get(), ix->a.d_row_hash.get(), keep * 8u, hipMemcpyDeviceToDevice, st));
+      KDB_TRY(hipMemcpyAsync(a.d_row_off.get(), ix->a.d_row_off.get(), keep * 4u, hipMemcpyDeviceToDevice, st));
+      KDB_TRY(hipMemcpyAsync(a.d_row_file.get(), ix->a.d_row_file.get(), keep * 4u, hipMemcpyDeviceToDevice, st));
+    }
+    a.row_cap = cap;
+    return hipSuccess;
+  }
+
+  // count -> scan -> parse over the ntiles tiles of the npf row regions in
+  // `files`, into row_hash() / row_off() / row_file() at each region's
+  // row_base; `reversed` for the staging of an open file.  tile_file names
+  // every tile's region (nullptr: there is one).  Synchronises; of the nf file
+  // slots, bad[i] != 0 where the region of slot bad_from + i is malformed.
+  hipError_t parse(hipStream_t st, const uint8_t* files, const ParseFile* pf, size_t npf, const uint32_t* tile_file,
+                   uint32_t ntiles, bool reversed, uint32_t nf, uint32_t bad_from, uint32_t bad_n, uint32_t* bad) {
+    KDB_TRY(upload(st, &d_pf, pf, npf));
+    if (tile_file) {
+      KDB_TRY(upload(st, &d_tile_file, tile_file, ntiles));
+    } else {
+      KDB_TRY(d_tile_file.alloc(ntiles));
+      KDB_TRY(hipMemsetAsync(d_tile_file.get(), 0, (size_t)ntiles * 4u, st));
+    }
+    KDB_TRY(d_tile_count.alloc(ntiles));
+    KDB_TRY(d_tile_prefix.alloc((size_t)ntiles + 1u));
+    KDB_TRY(d_malformed.alloc(nf));
+    KDB_TRY(hipMemsetAsync(d_malformed.get(), 0, (size_t)nf * 4u, st));
+    const auto count = reversed ? index_count_kernel<true> : index_count_kernel<false>;
+    const auto rows = reversed ? index_parse_kernel<true> : index_parse_kernel<false>;
+    hipLaunchKernelGGL(count, dim3(ntiles), dim3(kParseTile), 0, st, files, d_pf.get(), d_tile_file.get(),
+                       d_tile_count.get());
+    KDB_TRY(hipGetLastError());
+    KDB_TRY(launch_exclusive_scan(st, d_tile_count.get(), ntiles, d_tile_prefix.get(), d_tile_prefix.get() + ntiles));
+    // beyond every row the handle's lookups and scans read now
+    hipLaunchKernelGGL(rows, dim3(ntiles), dim3(kParseTile), 0, st, files, d_pf.get(), d_tile_file.get(),
+                       d_tile_prefix.get(), row_hash(), row_off(), row_file(), d_malformed.get());
+    KDB_TRY(hipGetLastError());
+    KDB_TRY(hipMemcpyAsync(bad, d_malformed.get() + bad_from, (size_t)bad_n * 4u, hipMemcpyDeviceToHost, st));
+    return hipStreamSynchronize(st);
+  }
+
+  // The buckets over rows [0, nrows) of row_hash() / row_off() / row_file():
+  // built from all resident rows, as a load builds them, whether B doubles or
+  // stays -- moving the old slots and placing only the new rows was measured
+  // and not kept.  No rows: no buckets, nbuckets = 0
+  // (the lookup asks the row count first).
+  hipError_t build_buckets(hipStream_t st, uint64_t nrows) {
+    rebuilt = true;
+    a.nbuckets = 0;
+    if (nrows == 0) return hipSuccess;
+    uint64_t B = 2;
+    while (B < 2u * nrows) B <<= 1;
+    const uint32_t n = (uint32_t)nrows;
+    KDB_TRY(a.d_start.alloc(B + 1u));
+    KDB_TRY(a.d_slots.alloc(nrows));
+    KDB_TRY(d_count.alloc(B));
+    KDB_TRY(hipMemsetAsync(d_count.get(), 0, B * 4u, st));
+    const uint32_t g = grid_for(n, 256, 2048);
+    hipLaunchKernelGGL(index_hist_kernel, dim3(g), dim3(256), 0, st, row_hash(), n, B - 1u, d_count.get());
+    KDB_TRY(hipGetLastError());
+    KDB_TRY(launch_exclusive_scan(st, d_count.get(), (uint32_t)B, a.d_start.get(), a.d_start.get() + B));
+    hipLaunchKernelGGL(index_fill_kernel, dim3(g), dim3(256), 0, st, row_hash(), row_off(), row_file(), n, B - 1u,
+                       a.d_start.get(), d_count.get(), a.d_slots.get());
+    KDB_TRY(hipGetLastError());
+    a.nbuckets = B;
+    return hipSuccess;
+  }
+
+  // Nothing can fail any more: the handle takes what was staged, this what it
+  // held.  The caller has synchronised.  The handle's prepared scan goes; a
+  // snapshot's list stands on rows that did not move.
+  void commit(kdb_index* to) {
+    IndexArrays& h = to->a;
+    h.d_file_off.swap(a.d_file_off);
+    h.d_file_size.swap(a.d_file_size);
+    h.d_fileid.swap(a.d_fileid);
+    h.d_file_rank.swap(a.d_file_rank);
+    h.d_rank_file.swap(a.d_rank_file);
+    if (rebuilt) {
+      h.d_start.swap(a.d_start);
+      h.d_slots.swap(a.d_slots);
+      h.nbuckets = a.nbuckets;
+    }
+    if (a.d_row_hash.get()) {
+      h.d_row_hash.swap(a.d_row_hash);
+      h.d_row_off.swap(a.d_row_off);
+      h.d_row_file.swap(a.d_row_file);
+      h.row_cap = a.row_cap;
+    }
+    if (closed_files) std::swap(h.host, a.host);
+    to->scan = ScanState{};
+  }
+};
 
 // The one way rows get into a handle.  The handle holds nfiles files (none:
 // the add is the load); the host arrays describe the nadd new ones, all in
-// ix->d_files.  The handle changes only at the end, in the swap.
+// ix->d_files.  The handle changes only at the end, in the commit.
 hipError_t index_add(kdb_index* ix, hipStream_t st, const uint64_t* file_off, const uint64_t* file_size,
                      const uint32_t* fileid, uint32_t nadd, int32_t* file_status, uint64_t* rows_added,
                      Refused* refused) {
   const uint8_t* d_files = ix->d_files;
   const uint32_t nf0 = ix->nfiles, nf = nf0 + nadd;
   const uint64_t nrows0 = ix->nrows;
-  // host arrays first, the device temporaries after them: hipFree waits for
-  // the copies that read these vectors before they go out of scope
-  std::vector<uint64_t> h_off(ix->file_off), h_size(ix->file_size), h_ts(ix->timestamp);
-  std::vector<uint32_t> h_id(ix->fileid), rank(ix->rank), rank_file(ix->rank_file);
-  std::vector<int32_t> h_status(ix->status);
-  std::vector<uint32_t> h_type(ix->filetype);
   std::vector<FileRec> rec(nadd);
   std::vector<int32_t> status(nadd);
   std::vector<uint32_t> order, tile_file, bad(nf);
   std::vector<ParseFile> pf;
-  AddTemps t;
-  h_off.insert(h_off.end(), file_off, file_off + nadd);
-  h_size.insert(h_size.end(), file_size, file_size + nadd);
-  h_id.insert(h_id.end(), fileid, fileid + nadd);
-  KDB_TRY(upload(st, &t.d_file_off, h_off.data(), nf));
-  KDB_TRY(upload(st, &t.d_file_size, h_size.data(), nf));
-  KDB_TRY(upload(st, &t.d_fileid, h_id.data(), nf));
+  DevBuf<uint32_t> d_mismatch;           // the pin's check
+  Staged s(ix, true);
+  DevBuf<FileRec> d_rec;
+  for (uint32_t f = 0; f < nadd; f++) s.append_file(file_off[f], file_size[f], fileid[f]);
+  KDB_TRY(s.upload_file_tables(st, nf));
   if (nadd) {
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_rec), nadd * sizeof(FileRec)));
-    hipLaunchKernelGGL(index_file_kernel, dim3(nadd), dim3(kFileBlock), 0, st, d_files, t.d_file_off + nf0,
-                       t.d_file_size + nf0, t.d_rec);
+    KDB_TRY(d_rec.alloc(nadd));
+    hipLaunchKernelGGL(index_file_kernel, dim3(nadd), dim3(kFileBlock), 0, st, d_files, s.a.d_file_off.get() + nf0,
+                       s.a.d_file_size.get() + nf0, d_rec.get());
     KDB_TRY(hipGetLastError());
-    KDB_TRY(hipMemcpyAsync(rec.data(), t.d_rec, nadd * sizeof(FileRec), hipMemcpyDeviceToHost, st));
+    KDB_TRY(hipMemcpyAsync(rec.data(), d_rec.get(), nadd * sizeof(FileRec), hipMemcpyDeviceToHost, st));
   }
   KDB_TRY(hipStreamSynchronize(st));
   for (uint32_t f = 0; f < nadd; f++) status[f] = rec[f].status;
 
   // LoadDatabase's order (:1007-1014): by (timestamp, fileid), the new files
   // among themselves; their rows are numbered after the rows the handle holds
-  uint64_t* row_hash = ix->d_row_hash;
-  uint32_t* row_off = ix->d_row_off;
-  uint32_t* row_file = ix->d_row_file;
-  uint64_t row_cap = ix->row_cap, rows_new = 0, rows_parsed = 0;
+  uint64_t rows_new = 0, rows_parsed = 0;
   for (;;) {
     order.clear();
     for (uint32_t f = 0; f < nadd; f++)
@@ -1041,39 +1078,16 @@ hipError_t index_add(kdb_index* ix, hipStream_t st, const uint64_t* file_off, co
       tile_file.insert(tile_file.end(), p.ntiles, (uint32_t)pf.size());
       pf.push_back(p);
     }
-    dfree(t.d_pf);
-    dfree(t.d_tile_file);
-    dfree(t.d_tile_count);
-    dfree(t.d_tile_prefix);
-    dfree(t.d_malformed);
     const uint32_t ntiles = (uint32_t)tile_file.size();
     if (rows_new == 0 || ntiles == 0) break;
-    if (nrows0 + rows_new > row_cap || (ix->tail.rows && !t.d_row_hash)) {
-      // the handle keeps its own arrays until the swap.  Later passes number
-      // fewer rows.  Rows of a tail lie where the new rows go and stay
-      // readable until the swap: the new rows go beside them then
-      KDB_TRY(grow_rows(ix, st, nrows0 + rows_new, nrows0, &t, &row_cap));
-      row_hash = t.d_row_hash;
-      row_off = t.d_row_off;
-      row_file = t.d_row_file;
-    }
-    KDB_TRY(upload(st, &t.d_pf, pf.data(), pf.size()));
-    KDB_TRY(upload(st, &t.d_tile_file, tile_file.data(), tile_file.size()));
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_tile_count), (size_t)ntiles * 4u));
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_tile_prefix), ((size_t)ntiles + 1u) * 8u));
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_malformed), (size_t)nf * 4u));
-    KDB_TRY(hipMemsetAsync(t.d_malformed, 0, (size_t)nf * 4u, st));
-    hipLaunchKernelGGL(index_count_kernel<false>, dim3(ntiles), dim3(kParseTile), 0, st, d_files, t.d_pf, t.d_tile_file,
-                       t.d_tile_count);
-    KDB_TRY(hipGetLastError());
-    KDB_TRY(launch_exclusive_scan(st, t.d_tile_count, ntiles, t.d_tile_prefix, t.d_tile_prefix + ntiles));
-    // rows [nrows0, nrows0 + rows_new): beyond what the handle's lookups read
-    hipLaunchKernelGGL(index_parse_kernel<false>, dim3(ntiles), dim3(kParseTile), 0, st, d_files, t.d_pf, t.d_tile_file,
-                       t.d_tile_prefix, row_hash, row_off, row_file, t.d_malformed);
-    KDB_TRY(hipGetLastError());
+    // the handle keeps its own arrays until the swap.  Later passes number
+    // fewer rows.  Rows of a tail lie where the new rows go and stay readable
+    // until the swap: the new rows go beside them then
+    if (nrows0 + rows_new > s.row_cap() || (ix->tail.rows && !s.a.d_row_hash.get()))
+      KDB_TRY(s.grow_rows(st, nrows0 + rows_new, nrows0));
+    // rows [nrows0, nrows0 + rows_new)
+    KDB_TRY(s.parse(st, d_files, pf.data(), pf.size(), tile_file.data(), ntiles, false, nf, 0, nf, bad.data()));
     rows_parsed += rows_new;
-    KDB_TRY(hipMemcpyAsync(bad.data(), t.d_malformed, (size_t)nf * 4u, hipMemcpyDeviceToHost, st));
-    KDB_TRY(hipStreamSynchronize(st));
     bool again = false;
     for (uint32_t f = 0; f < nadd; f++)
       if (bad[nf0 + f] && status[f] == 0) {
@@ -1082,15 +1096,11 @@ hipError_t index_add(kdb_index* ix, hipStream_t st, const uint64_t* file_off, co
       }
     if (!again) break;
   }
-  // a fresh load of all the files numbers the new rows after the loaded ones
-  // only if every new file sorts after every loaded one
   for (uint32_t f : order)
-    for (uint32_t o = 0; o < nf0; o++)
-      if (h_status[o] == 0 && (rec[f].timestamp < h_ts[o] || (rec[f].timestamp == h_ts[o] && fileid[f] <= h_id[o]))) {
-        status[f] = KDB_INDEX_FILE_ORDER;
-        *refused = Refused::kOrder;
-        break;
-      }
+    if (!sorts_after_loaded(ix, rec[f].timestamp, fileid[f])) {
+      status[f] = KDB_INDEX_FILE_ORDER;
+      *refused = Refused::kOrder;
+    }
   for (uint32_t f = 0; f < nadd; f++) file_status[f] = status[f];
   if (*refused != Refused::kNo) return hipSuccess;
 
@@ -1107,20 +1117,20 @@ hipError_t index_add(kdb_index* ix, hipStream_t st, const uint64_t* file_off, co
       rq.num_entries = rec[f].num_entries;
     }
     // rows held and rows parsed lie in arrays of their own (a tail with rows forces grow_rows above)
-    if (!lp::allows(pin, rq) || (pin.rows && row_hash == ix->d_row_hash)) {
+    if (!lp::allows(pin, rq) || (pin.rows && !s.a.d_row_hash.get())) {
       *refused = Refused::kPinned;
       return hipSuccess;
     }
     if (pin.rows) {
       uint32_t mismatch = 0;
       const uint32_t n = (uint32_t)pin.rows;
-      KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_mismatch), 4u));
-      KDB_TRY(hipMemsetAsync(t.d_mismatch, 0, 4u, st));
-      hipLaunchKernelGGL(index_rows_equal_kernel, dim3(std::min<uint32_t>((n + 255u) / 256u, 2048u)), dim3(256), 0, st,
-                         ix->d_row_hash + nrows0, ix->d_row_off + nrows0, row_hash + nrows0, row_off + nrows0, n,
-                         t.d_mismatch);
+      KDB_TRY(d_mismatch.alloc(1));
+      KDB_TRY(hipMemsetAsync(d_mismatch.get(), 0, 4u, st));
+      hipLaunchKernelGGL(index_rows_equal_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, st,
+                         ix->a.d_row_hash.get() + nrows0, ix->a.d_row_off.get() + nrows0, s.row_hash() + nrows0,
+                         s.row_off() + nrows0, n, d_mismatch.get());
       KDB_TRY(hipGetLastError());
-      KDB_TRY(hipMemcpyAsync(&mismatch, t.d_mismatch, 4u, hipMemcpyDeviceToHost, st));
+      KDB_TRY(hipMemcpyAsync(&mismatch, d_mismatch.get(), 4u, hipMemcpyDeviceToHost, st));
       KDB_TRY(hipStreamSynchronize(st));
       if (mismatch) {
         *refused = Refused::kPinned;
@@ -1130,60 +1140,32 @@ hipError_t index_add(kdb_index* ix, hipStream_t st, const uint64_t* file_off, co
   }
 
   // the scan orders by the file's rank; a file that did not load has no rows and no rank
-  rank.resize(nf, 0xFFFFFFFFu);
-  rank_file.resize(nf, 0u);
+  HostFiles& h = s.a.host;
+  h.rank.resize(nf, 0xFFFFFFFFu);
+  h.rank_file.resize(nf, 0u);
   for (uint32_t i = 0; i < order.size(); i++) {
-    rank[nf0 + order[i]] = ix->nloaded + i;
-    rank_file[ix->nloaded + i] = nf0 + order[i];
+    h.rank[nf0 + order[i]] = ix->nloaded + i;
+    h.rank_file[ix->nloaded + i] = nf0 + order[i];
   }
-  KDB_TRY(upload(st, &t.d_file_rank, rank.data(), nf));
-  KDB_TRY(upload(st, &t.d_rank_file, rank_file.data(), nf));
-
-  const uint64_t nrows = nrows0 + rows_new;
-  uint64_t B = ix->nbuckets;
-  // rows of a tail leave the buckets with it, also where no row comes in
-  const bool rebuild = rows_new || ix->tail.rows;
-  if (rebuild) KDB_TRY(build_buckets(st, row_hash, row_off, row_file, nrows, &t, &B));
+  KDB_TRY(s.upload_ranks(st, nf));
   for (uint32_t f = 0; f < nadd; f++) {
-    h_ts.push_back(rec[f].timestamp);
-    h_type.push_back(rec[f].filetype);
-    h_status.push_back(status[f]);
+    h.timestamp.push_back(rec[f].timestamp);
+    h.filetype.push_back(rec[f].filetype);
+    h.status.push_back(status[f]);
   }
+  const uint64_t nrows = nrows0 + rows_new;
+  // rows of a tail leave the buckets with it, also where no row comes in
+  if (rows_new || ix->tail.rows) KDB_TRY(s.build_buckets(st, nrows));
   KDB_TRY(hipStreamSynchronize(st));
 
-  // nothing can fail any more: the handle takes what was built, `t` what it held
-  std::swap(ix->d_file_off, t.d_file_off);
-  std::swap(ix->d_file_size, t.d_file_size);
-  std::swap(ix->d_fileid, t.d_fileid);
-  std::swap(ix->d_file_rank, t.d_file_rank);
-  std::swap(ix->d_rank_file, t.d_rank_file);
-  if (rebuild) {
-    std::swap(ix->d_start, t.d_start);
-    std::swap(ix->d_slots, t.d_slots);
-  }
-  if (t.d_row_hash) {
-    std::swap(ix->d_row_hash, t.d_row_hash);
-    std::swap(ix->d_row_off, t.d_row_off);
-    std::swap(ix->d_row_file, t.d_row_file);
-    ix->row_cap = row_cap;
-  }
-  ix->file_off.swap(h_off);
-  ix->file_size.swap(h_size);
-  ix->fileid.swap(h_id);
-  ix->timestamp.swap(h_ts);
-  ix->filetype.swap(h_type);
-  ix->status.swap(h_status);
-  ix->rank.swap(rank);
-  ix->rank_file.swap(rank_file);
+  s.commit(ix);
   ix->nloaded += (uint32_t)order.size();
   ix->nfiles = nf;
   ix->nrows = nrows;
-  ix->nbuckets = B;
-  scan_release(&ix->scan);               // the handle's own; a snapshot's list stands on rows that did not move
   ix->add_done = true;
   ix->add_rows_parsed = rows_parsed;
   ix->tail = kdb_index::Tail{};          // the file that was open arrives closed, or has: its rows are numbered as they were
-  for (kdb_snapshot* s : ix->pins) s->pinned = false;      // checked above: from here on ordinary prefix snapshots
+  for (kdb_snapshot* sn : ix->pins) sn->pinned = false;    // checked above: from here on ordinary prefix snapshots
   ix->pins.clear();
   *rows_added = rows_new;
   return hipSuccess;
@@ -1192,7 +1174,7 @@ hipError_t index_add(kdb_index* ix, hipStream_t st, const uint64_t* file_off, co
 // kdb_index_set_tail (f) and kdb_index_drop_tail (f == nullptr): the handle's
 // per-file arrays with the open file in the next slot and rank, its staged
 // rows parsed behind the closed files' rows, the buckets over all of them;
-// built beside the handle and swapped in at the end, like an add.
+// built beside the handle and committed at the end, like an add.
 hipError_t index_tail(kdb_index* ix, hipStream_t st, const kdb_open_file* f, bool reparse, uint64_t* gained,
                       bool* refused) {
   const kdb_index::Tail held = ix->tail;
@@ -1211,10 +1193,7 @@ hipError_t index_tail(kdb_index* ix, hipStream_t st, const kdb_open_file* f, boo
       return hipSuccess;
     if (!ir::tail_range_ok(hr, hb, f->rows, f->row_bytes, f->rows_last)) return hipSuccess;
     // it closes after every loaded file: index_add's order rule, ahead of time
-    for (uint32_t o = 0; o < nf0; o++)
-      if (ix->status[o] == 0 && (f->timestamp < ix->timestamp[o] ||
-                                 (f->timestamp == ix->timestamp[o] && f->fileid <= ix->fileid[o])))
-        return hipSuccess;
+    if (!sorts_after_loaded(ix, f->timestamp, f->fileid)) return hipSuccess;
     *refused = false;
     if (incremental && f->rows == held.rows && f->row_bytes == held.row_bytes && f->bytes == held.bytes) {
       ix->tail_rows_parsed = 0;            // nothing was appended: nothing changes
@@ -1222,40 +1201,23 @@ hipError_t index_tail(kdb_index* ix, hipStream_t st, const kdb_open_file* f, boo
       return hipSuccess;
     }
   }
-  // host arrays first, the device temporaries after them (see index_add)
-  std::vector<uint64_t> h_off(ix->file_off), h_size(ix->file_size);
-  std::vector<uint32_t> h_id(ix->fileid), rank(ix->rank), rank_file(ix->rank_file);
+  ParseFile p{};
   uint32_t bad = 0;
-  AddTemps t;
+  Staged s(ix, false);
   if (f) {
-    h_off.push_back(f->file_off);
-    h_size.push_back(f->bytes);
-    h_id.push_back(f->fileid);
-    rank.push_back(ix->nloaded);
-    rank_file.resize(nf, 0u);
-    rank_file[ix->nloaded] = nf0;
+    s.append_file(f->file_off, f->bytes, f->fileid);
+    s.a.host.rank.push_back(ix->nloaded);
+    s.a.host.rank_file.resize(nf, 0u);
+    s.a.host.rank_file[ix->nloaded] = nf0;
   }
-  KDB_TRY(upload(st, &t.d_file_off, h_off.data(), nf));
-  KDB_TRY(upload(st, &t.d_file_size, h_size.data(), nf));
-  KDB_TRY(upload(st, &t.d_fileid, h_id.data(), nf));
-  KDB_TRY(upload(st, &t.d_file_rank, rank.data(), nf));
-  KDB_TRY(upload(st, &t.d_rank_file, rank_file.data(), nf));
+  KDB_TRY(s.upload_file_tables(st, nf));
+  KDB_TRY(s.upload_ranks(st, nf));
 
-  uint64_t* row_hash = ix->d_row_hash;
-  uint32_t* row_off = ix->d_row_off;
-  uint32_t* row_file = ix->d_row_file;
-  uint64_t row_cap = ix->row_cap;
   const uint64_t parsed = trows - hr;
   if (parsed) {
     // rows [nrows0 + hr, nrows): in place only where they lie beyond every
     // row the handle's lookups and scans read now
-    if (!incremental || nrows > row_cap) {
-      KDB_TRY(grow_rows(ix, st, nrows, nrows0 + hr, &t, &row_cap));
-      row_hash = t.d_row_hash;
-      row_off = t.d_row_off;
-      row_file = t.d_row_file;
-    }
-    ParseFile p{};
+    if (!incremental || nrows > ix->a.row_cap) KDB_TRY(s.grow_rows(st, nrows, nrows0 + hr));
     p.reg_len = f->row_bytes - hb;         // >= 2 * parsed
     p.reg_off = f->rows_last - hb;         // staged byte hb; the range ends at rows_last - (row_bytes - 1) >= 0
     p.nvar = 2u * parsed;
@@ -1263,59 +1225,19 @@ hipError_t index_tail(kdb_index* ix, hipStream_t st, const kdb_open_file* f, boo
     p.first_tile = 0;
     p.ntiles = (uint32_t)((p.reg_len + kParseTile - 1u) / kParseTile);   // reg_len <= 15 * 2^30
     p.slot = nf0;
-    const uint32_t ntiles = p.ntiles;
-    KDB_TRY(upload(st, &t.d_pf, &p, 1));
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_tile_file), (size_t)ntiles * 4u));
-    KDB_TRY(hipMemsetAsync(t.d_tile_file, 0, (size_t)ntiles * 4u, st));
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_tile_count), (size_t)ntiles * 4u));
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_tile_prefix), ((size_t)ntiles + 1u) * 8u));
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_malformed), (size_t)nf * 4u));
-    KDB_TRY(hipMemsetAsync(t.d_malformed, 0, (size_t)nf * 4u, st));
-    hipLaunchKernelGGL(index_count_kernel<true>, dim3(ntiles), dim3(kParseTile), 0, st, ix->d_files, t.d_pf,
-                       t.d_tile_file, t.d_tile_count);
-    KDB_TRY(hipGetLastError());
-    KDB_TRY(launch_exclusive_scan(st, t.d_tile_count, ntiles, t.d_tile_prefix, t.d_tile_prefix + ntiles));
-    hipLaunchKernelGGL(index_parse_kernel<true>, dim3(ntiles), dim3(kParseTile), 0, st, ix->d_files, t.d_pf,
-                       t.d_tile_file, t.d_tile_prefix, row_hash, row_off, row_file, t.d_malformed);
-    KDB_TRY(hipGetLastError());
-    KDB_TRY(hipMemcpyAsync(&bad, t.d_malformed + nf0, 4u, hipMemcpyDeviceToHost, st));
-    KDB_TRY(hipStreamSynchronize(st));
-    if (bad) {                             // not two varints per row, or one too long
+    KDB_TRY(s.parse(st, ix->d_files, &p, 1, nullptr, p.ntiles, true, nf, nf0, 1, &bad));
+    if (bad) {                        // not two varints per row, or one too long
       *refused = true;
       return hipSuccess;
     }
   }
-  uint64_t B = 0;
-  KDB_TRY(build_buckets(st, row_hash, row_off, row_file, nrows, &t, &B));
+  KDB_TRY(s.build_buckets(st, nrows));
   KDB_TRY(hipStreamSynchronize(st));
 
-  // nothing can fail any more
-  std::swap(ix->d_file_off, t.d_file_off);
-  std::swap(ix->d_file_size, t.d_file_size);
-  std::swap(ix->d_fileid, t.d_fileid);
-  std::swap(ix->d_file_rank, t.d_file_rank);
-  std::swap(ix->d_rank_file, t.d_rank_file);
-  std::swap(ix->d_start, t.d_start);
-  std::swap(ix->d_slots, t.d_slots);
-  if (t.d_row_hash) {
-    std::swap(ix->d_row_hash, t.d_row_hash);
-    std::swap(ix->d_row_off, t.d_row_off);
-    std::swap(ix->d_row_file, t.d_row_file);
-    ix->row_cap = row_cap;
-  }
-  ix->nbuckets = B;
-  ix->tail = kdb_index::Tail{};
-  if (f) {
-    ix->tail.held = true;
-    ix->tail.fileid = f->fileid;
-    ix->tail.timestamp = f->timestamp;
-    ix->tail.file_off = f->file_off;
-    ix->tail.bytes = f->bytes;
-    ix->tail.rows = f->rows;
-    ix->tail.row_bytes = f->row_bytes;
-  }
+  s.commit(ix);
+  ix->tail = f ? kdb_index::Tail{true, f->fileid, f->timestamp, f->file_off, f->bytes, f->rows, f->row_bytes}
+               : kdb_index::Tail{};
   ix->tail_rows_parsed = parsed;
-  scan_release(&ix->scan);                 // the handle's own; a snapshot's list stands on rows below its limit
   *gained = grows ? trows - held.rows : trows;
   return hipSuccess;
 }
@@ -1334,7 +1256,6 @@ extern "C" int kdb_index_create(uint32_t hash_type, kdb_index** ix) {
 
 extern "C" int kdb_index_destroy(kdb_index* ix) {
   if (!ix || ix->snapshots) return KDB_PUT_EINVAL;
-  index_release(ix);
   delete ix;
   return KDB_PUT_OK;
 }
@@ -1390,7 +1311,7 @@ extern "C" int kdb_index_add_files(kdb_index* ix, void* stream, const uint8_t* d
 extern "C" int kdb_index_add_stats(const kdb_index* ix, uint32_t* merged, uint64_t* nbuckets, uint64_t* rows_parsed) {
   if (!ix || !ix->add_done) return KDB_PUT_EINVAL;
   if (merged) *merged = 0u;                // the buckets are always rebuilt
-  if (nbuckets) *nbuckets = ix->nbuckets;
+  if (nbuckets) *nbuckets = ix->a.nbuckets;
   if (rows_parsed) *rows_parsed = ix->add_rows_parsed;
   return KDB_PUT_OK;
 }
@@ -1433,18 +1354,19 @@ extern "C" int kdb_index_tail_stats(const kdb_index* ix, uint32_t* held, uint32_
   if (rows) *rows = ix->tail.rows;
   if (bytes) *bytes = ix->tail.bytes;
   if (rows_parsed_last) *rows_parsed_last = ix->tail_rows_parsed;
-  if (nbuckets) *nbuckets = ix->nbuckets;
+  if (nbuckets) *nbuckets = ix->a.nbuckets;
   return KDB_PUT_OK;
 }
 
 // kdb_compact.h: the timestamp the compacted files lock (storage_engine.h:806-810, 927-934)
 extern "C" int kdb_index_view_timestamp(const kdb_index* ix, uint32_t nfiles, uint64_t* timestamp_max) {
   if (!ix || !timestamp_max || nfiles > ix->nfiles) return KDB_PUT_EINVAL;
+  const HostFiles& h = ix->a.host;
   uint64_t ts = 0;
   for (uint32_t f = 0; f < nfiles; f++) {
-    if (ix->status[f] != 0) continue;
-    if (ix->filetype[f] & 4u) return KDB_PUT_EINVAL;     // kCompactedLargeType
-    ts = std::max(ts, ix->timestamp[f]);
+    if (h.status[f] != 0) continue;
+    if (h.filetype[f] & 4u) return KDB_PUT_EINVAL;       // kCompactedLargeType
+    ts = std::max(ts, h.timestamp[f]);
   }
   *timestamp_max = ts;
   return KDB_PUT_OK;
@@ -1461,13 +1383,13 @@ extern "C" int kdb_index_pairs(const kdb_index* ix, uint64_t* hash_out, uint64_t
   if (ix->visible_rows() == 0) return KDB_PUT_OK;
   const size_t n = (size_t)ix->visible_rows();
   std::vector<uint32_t> off(n), file(n);
-  hipError_t e = hipMemcpy(hash_out, ix->d_row_hash, n * 8u, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(off.data(), ix->d_row_off, n * 4u, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(file.data(), ix->d_row_file, n * 4u, hipMemcpyDeviceToHost);
+  hipError_t e = hipMemcpy(hash_out, ix->a.d_row_hash.get(), n * 8u, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(off.data(), ix->a.d_row_off.get(), n * 4u, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(file.data(), ix->a.d_row_file.get(), n * 4u, hipMemcpyDeviceToHost);
   if (e != hipSuccess) return hip_code(e);
   for (size_t r = 0; r < n; r++) {
     if (file[r] >= ix->nfiles + (ix->tail.held ? 1u : 0u)) return KDB_PUT_EHIP;
-    const uint32_t id = file[r] < ix->nfiles ? ix->fileid[file[r]] : ix->tail.fileid;   // the tail's slot is the next one
+    const uint32_t id = file[r] < ix->nfiles ? ix->a.host.fileid[file[r]] : ix->tail.fileid;   // the tail's slot is the next one
     location_out[r] = (uint64_t)id << 32 | off[r];
   }
   return KDB_PUT_OK;
@@ -1477,6 +1399,36 @@ extern "C" uint64_t kdb_index_get_scratch_bytes(uint32_t n) { return (uint64_t)n
 
 namespace {
 
+// The handle's arrays as they are now; nrows is the handle's row count, or a
+// snapshot's row limit (index_get_kernel<true>, index_live_kernel<true>).
+IndexView view_of(const kdb_index* ix, uint64_t nrows) {
+  const IndexArrays& a = ix->a;
+  return IndexView{ix->d_files,     a.d_file_off.get(), a.d_file_size.get(),         a.d_fileid.get(), a.d_start.get(),
+                   a.d_slots.get(), a.nbuckets ? a.nbuckets - 1u : 0u, (uint32_t)nrows, ix->hash_type};
+}
+
+// Workgroups of kGetBlock threads for n items, a wave each.
+uint32_t wave_grid(uint32_t n) { return grid_for(n, kGetBlock / 64, 16384); }
+
+// What a lookup batch and a scan batch do before their kernel:
+// internal__size_multipart_required where the caller names none, the summary cleared.
+hipError_t batch_begin(hipStream_t st, uint64_t* multipart_required, uint64_t* summary) {
+  if (*multipart_required == 0) *multipart_required = 1048576u;
+  return hipMemsetAsync(summary, 0, 5 * 8, st);
+}
+
+// And after it (`launched`: what the launch left): the 64-byte-aligned output
+// slots and what the host needs to size the decode, over n >= 1 items.
+int batch_end(hipStream_t st, hipError_t launched, const uint32_t* slot_len, uint32_t n, uint64_t* out_off,
+              const uint64_t* avail, const uint64_t* size, const int32_t* status, uint64_t* summary) {
+  hipError_t e = launched;
+  if (e == hipSuccess) e = launch_exclusive_scan(st, slot_len, n, out_off, summary + 1);
+  if (e != hipSuccess) return hip_code(e);
+  hipLaunchKernelGGL(index_summary_kernel, dim3(grid_for(n, 256, 1024)), dim3(256), 0, st, avail, size, status, n,
+                     reinterpret_cast<unsigned long long*>(summary));
+  return hip_code(hipGetLastError());
+}
+
 // kdb_index_get_batch (snap = nullptr) and kdb_snapshot_get_batch: the same
 // checks, scan and summary around index_get_kernel<false> and <true>.
 int lookup_batch(const kdb_index* ix, const kdb_snapshot* snap, void* stream, const uint8_t* keys,
@@ -1484,38 +1436,22 @@ int lookup_batch(const kdb_index* ix, const kdb_snapshot* snap, void* stream, co
                  uint64_t multipart_required, uint8_t* scratch, uint64_t scratch_bytes, uint64_t* stored_off,
                  uint64_t* avail, uint64_t* svc, uint64_t* size, uint32_t* checksum, uint32_t* checksum_initial,
                  uint64_t* out_off, uint64_t* location, int32_t* status, uint64_t* summary) {
-  if (multipart_required == 0) multipart_required = 1048576u;    // internal__size_multipart_required
   if (!ix || !summary || verify_header < 0 || verify_header > 1 || multipart_required > (1ull << 31) ||
       scratch_bytes < kdb_index_get_scratch_bytes(n) ||
       (n && (!keys || !key_off || !key_len || !scratch || !stored_off || !avail || !svc || !size || !checksum ||
              !checksum_initial || !out_off || !location || !status)))
     return KDB_PUT_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(summary, 0, 5 * 8, st);
+  const hipError_t e = batch_begin(st, &multipart_required, summary);
   if (e != hipSuccess) return hip_code(e);
   if (n == 0) return KDB_PUT_OK;
   uint32_t* slot_len = reinterpret_cast<uint32_t*>(scratch);
   // a snapshot: the handle's arrays as they are now, the row count its own limit
-  const IndexView view{ix->d_files,  ix->d_file_off, ix->d_file_size,        ix->d_fileid, ix->d_start,
-                       ix->d_slots,  ix->nbuckets ? ix->nbuckets - 1u : 0u, (uint32_t)(snap ? snap->nrows : ix->visible_rows()),
-                       ix->hash_type};
-  const uint32_t waves = kGetBlock / 64;
-  const uint32_t g = std::min<uint32_t>((n + waves - 1u) / waves, 16384u);
-  if (snap)
-    hipLaunchKernelGGL(index_get_kernel<true>, dim3(g), dim3(kGetBlock), 0, st, view, keys, key_off, key_len, n,
-                       verify_header, multipart_required, stored_off, avail, svc, size, checksum, checksum_initial,
-                       slot_len, location, status);
-  else
-    hipLaunchKernelGGL(index_get_kernel<false>, dim3(g), dim3(kGetBlock), 0, st, view, keys, key_off, key_len, n,
-                       verify_header, multipart_required, stored_off, avail, svc, size, checksum, checksum_initial,
-                       slot_len, location, status);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = launch_exclusive_scan(st, slot_len, n, out_off, summary + 1);
-  if (e != hipSuccess) return hip_code(e);
-  const uint32_t sg = std::min<uint32_t>((n + 255u) / 256u, 1024u);
-  hipLaunchKernelGGL(index_summary_kernel, dim3(sg), dim3(256), 0, st, avail, size, status, n,
-                     reinterpret_cast<unsigned long long*>(summary));
-  return hip_code(hipGetLastError());
+  const auto get = snap ? index_get_kernel<true> : index_get_kernel<false>;
+  hipLaunchKernelGGL(get, dim3(wave_grid(n)), dim3(kGetBlock), 0, st, view_of(ix, snap ? snap->nrows : ix->visible_rows()),
+                     keys, key_off, key_len, n, verify_header, multipart_required, stored_off, avail, svc, size,
+                     checksum, checksum_initial, slot_len, location, status);
+  return batch_end(st, hipGetLastError(), slot_len, n, out_off, avail, size, status, summary);
 }
 
 }  // namespace
@@ -1536,26 +1472,11 @@ namespace {
 
 // Temporaries of one prepare, freed on every way out.
 struct ScanTemps {
-  uint32_t* d_flag = nullptr;
-  uint32_t* d_klen = nullptr;
-  uint64_t* d_pos = nullptr;             // nrows + 1: the last is the live count
-  unsigned long long* d_stats = nullptr;
-  uint32_t* d_list_klen = nullptr;
-  ~ScanTemps() {
-    dfree(d_flag);
-    dfree(d_klen);
-    dfree(d_pos);
-    dfree(d_stats);
-    dfree(d_list_klen);
-  }
+  DevBuf<uint32_t> d_list_klen;
+  DevBuf<unsigned long long> d_stats;
+  DevBuf<uint64_t> d_pos;                // nrows + 1: the last is the live count
+  DevBuf<uint32_t> d_klen, d_flag;
 };
-
-// The handle's arrays as they are now; nrows is the handle's row count, or a
-// snapshot's row limit (index_get_kernel<true>, index_live_kernel<true>).
-IndexView view_of(const kdb_index* ix, uint64_t nrows) {
-  return IndexView{ix->d_files, ix->d_file_off, ix->d_file_size,        ix->d_fileid, ix->d_start,
-                   ix->d_slots, ix->nbuckets ? ix->nbuckets - 1u : 0u, (uint32_t)nrows, ix->hash_type};
-}
 
 // The liveness pass and the ordered list over the handle's first nrows rows,
 // into `sc`: all the handle's rows for its own scan (limited = false), a
@@ -1565,31 +1486,27 @@ IndexView view_of(const kdb_index* ix, uint64_t nrows) {
 // among them are the exclusive sum of the flags read at that row.
 hipError_t scan_prepare(const kdb_index* ix, ScanState* sc, uint64_t nrows, uint64_t closed_rows, bool limited,
                         hipStream_t st, int verify_header, uint64_t* stats_out) {
-  ScanTemps t;
-  const uint32_t n = (uint32_t)nrows;
   unsigned long long stats[3] = {0, 0, 0};
   uint64_t live = 0, closed_live = 0;
+  ScanTemps t;
+  const uint32_t n = (uint32_t)nrows;
   const bool below_tail = closed_rows < nrows;
   if (n) {
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_flag), (size_t)n * 4u));
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_klen), (size_t)n * 4u));
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_pos), ((size_t)n + 1u) * 8u));
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_stats), sizeof stats));
-    KDB_TRY(hipMemsetAsync(t.d_stats, 0, sizeof stats, st));
-    const RowView rows{ix->d_row_hash, ix->d_row_off, ix->d_row_file, ix->d_file_rank};
-    const uint32_t waves = kGetBlock / 64;
-    const uint32_t g = std::min<uint32_t>((n + waves - 1u) / waves, 16384u);
-    if (limited)
-      hipLaunchKernelGGL(index_live_kernel<true>, dim3(g), dim3(kGetBlock), 0, st, view_of(ix, nrows), rows,
-                         verify_header, t.d_flag, t.d_klen, t.d_stats);
-    else
-      hipLaunchKernelGGL(index_live_kernel<false>, dim3(g), dim3(kGetBlock), 0, st, view_of(ix, nrows), rows,
-                         verify_header, t.d_flag, t.d_klen, t.d_stats);
+    KDB_TRY(t.d_flag.alloc(n));
+    KDB_TRY(t.d_klen.alloc(n));
+    KDB_TRY(t.d_pos.alloc((size_t)n + 1u));
+    KDB_TRY(t.d_stats.alloc(3));
+    KDB_TRY(hipMemsetAsync(t.d_stats.get(), 0, sizeof stats, st));
+    const RowView rows{ix->a.d_row_hash.get(), ix->a.d_row_off.get(), ix->a.d_row_file.get(), ix->a.d_file_rank.get()};
+    const auto alive = limited ? index_live_kernel<true> : index_live_kernel<false>;
+    hipLaunchKernelGGL(alive, dim3(wave_grid(n)), dim3(kGetBlock), 0, st, view_of(ix, nrows), rows, verify_header,
+                       t.d_flag.get(), t.d_klen.get(), t.d_stats.get());
     KDB_TRY(hipGetLastError());
-    KDB_TRY(launch_exclusive_scan(st, t.d_flag, n, t.d_pos, t.d_pos + n));
-    KDB_TRY(hipMemcpyAsync(&live, t.d_pos + n, 8, hipMemcpyDeviceToHost, st));
-    if (below_tail) KDB_TRY(hipMemcpyAsync(&closed_live, t.d_pos + closed_rows, 8, hipMemcpyDeviceToHost, st));
-    KDB_TRY(hipMemcpyAsync(stats, t.d_stats, sizeof stats, hipMemcpyDeviceToHost, st));
+    KDB_TRY(launch_exclusive_scan(st, t.d_flag.get(), n, t.d_pos.get(), t.d_pos.get() + n));
+    KDB_TRY(hipMemcpyAsync(&live, t.d_pos.get() + n, 8, hipMemcpyDeviceToHost, st));
+    if (below_tail)
+      KDB_TRY(hipMemcpyAsync(&closed_live, t.d_pos.get() + closed_rows, 8, hipMemcpyDeviceToHost, st));
+    KDB_TRY(hipMemcpyAsync(stats, t.d_stats.get(), sizeof stats, hipMemcpyDeviceToHost, st));
     KDB_TRY(hipStreamSynchronize(st));
     // iterator order is (file rank, offset): the compaction gives it unless
     // some file's rows do not ascend; then the list is sorted, padded to a
@@ -1599,22 +1516,22 @@ hipError_t scan_prepare(const kdb_index* ix, ScanState* sc, uint64_t nrows, uint
       cap = 2;
       while (cap < live) cap <<= 1;
     }
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&sc->d_live), std::max<uint64_t>(cap, 1) * 8u));
-    KDB_TRY(hipMalloc(reinterpret_cast<void**>(&t.d_list_klen), std::max<uint64_t>(cap, 1) * 4u));
+    KDB_TRY(sc->d_live.alloc(std::max<uint64_t>(cap, 1)));
+    KDB_TRY(t.d_list_klen.alloc(std::max<uint64_t>(cap, 1)));
     if (cap > live) {
-      KDB_TRY(hipMemsetAsync(sc->d_live, 0xFF, cap * 8u, st));
-      KDB_TRY(hipMemsetAsync(t.d_list_klen, 0, cap * 4u, st));
+      KDB_TRY(hipMemsetAsync(sc->d_live.get(), 0xFF, cap * 8u, st));
+      KDB_TRY(hipMemsetAsync(t.d_list_klen.get(), 0, cap * 4u, st));
     }
-    const uint32_t sg = std::min<uint32_t>((n + 255u) / 256u, 2048u);
-    hipLaunchKernelGGL(index_live_scatter_kernel, dim3(sg), dim3(256), 0, st, rows, n, t.d_flag, t.d_klen, t.d_pos,
-                       sc->d_live, t.d_list_klen);
+    hipLaunchKernelGGL(index_live_scatter_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, st, rows, n,
+                       t.d_flag.get(), t.d_klen.get(), t.d_pos.get(), sc->d_live.get(), t.d_list_klen.get());
     KDB_TRY(hipGetLastError());
     if (cap > live || (stats[0] && live > 1)) {
       const uint32_t m = (uint32_t)cap;
-      const uint32_t bg = std::min<uint32_t>((m + 255u) / 256u, 2048u);
+      const uint32_t bg = grid_for(m, 256, 2048);
       for (uint32_t k = 2; k != 0 && k <= m; k <<= 1)
         for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-          hipLaunchKernelGGL(index_bitonic_kernel, dim3(bg), dim3(256), 0, st, sc->d_live, t.d_list_klen, m, k, j);
+          hipLaunchKernelGGL(index_bitonic_kernel, dim3(bg), dim3(256), 0, st, sc->d_live.get(), t.d_list_klen.get(),
+                             m, k, j);
           sc->sort_steps++;
         }
       KDB_TRY(hipGetLastError());
@@ -1623,13 +1540,14 @@ hipError_t scan_prepare(const kdb_index* ix, ScanState* sc, uint64_t nrows, uint
   sc->live = live;
   sc->closed_live = below_tail ? closed_live : live;
   sc->key_prefix.assign((size_t)live + 1u, 0);
-  KDB_TRY(hipMalloc(reinterpret_cast<void**>(&sc->d_key_prefix), ((size_t)live + 1u) * 8u));
+  KDB_TRY(sc->d_key_prefix.alloc((size_t)live + 1u));
   if (live) {
-    KDB_TRY(launch_exclusive_scan(st, t.d_list_klen, (uint32_t)live, sc->d_key_prefix, sc->d_key_prefix + live));
-    KDB_TRY(hipMemcpyAsync(sc->key_prefix.data(), sc->d_key_prefix, ((size_t)live + 1u) * 8u,
+    KDB_TRY(launch_exclusive_scan(st, t.d_list_klen.get(), (uint32_t)live, sc->d_key_prefix.get(),
+                                  sc->d_key_prefix.get() + live));
+    KDB_TRY(hipMemcpyAsync(sc->key_prefix.data(), sc->d_key_prefix.get(), ((size_t)live + 1u) * 8u,
                            hipMemcpyDeviceToHost, st));
   } else {
-    KDB_TRY(hipMemsetAsync(sc->d_key_prefix, 0, 8, st));
+    KDB_TRY(hipMemsetAsync(sc->d_key_prefix.get(), 0, 8, st));
   }
   KDB_TRY(hipStreamSynchronize(st));
   stats_out[0] = live;
@@ -1641,16 +1559,16 @@ hipError_t scan_prepare(const kdb_index* ix, ScanState* sc, uint64_t nrows, uint
 // kdb_index_scan_prepare and kdb_snapshot_scan_prepare.
 int scan_prepare_checked(const kdb_index* ix, ScanState* sc, uint64_t nrows, uint64_t closed_rows, bool limited,
                          void* stream, int verify_header, uint64_t* live, uint64_t* key_bytes, uint32_t* max_key_len) {
-  scan_release(sc);
+  *sc = ScanState{};
   uint64_t stats[3] = {0, 0, 0};
   const hipError_t e = scan_prepare(ix, sc, nrows, closed_rows, limited, (hipStream_t)stream, verify_header, stats);
   if (e != hipSuccess) {
-    scan_release(sc);
+    *sc = ScanState{};
     return hip_code(e);
   }
   // the list's own sum of key lengths and the liveness pass's must agree
   if (sc->key_prefix.back() != stats[1]) {
-    scan_release(sc);
+    *sc = ScanState{};
     return KDB_PUT_EHIP;
   }
   sc->ready = true;
@@ -1667,7 +1585,6 @@ int scan_batch(const kdb_index* ix, const ScanState* sc, uint64_t nrows, void* s
                uint64_t keys_cap, uint64_t* key_off, uint32_t* key_len, uint64_t* stored_off, uint64_t* avail,
                uint64_t* svc, uint64_t* size, uint32_t* checksum, uint32_t* checksum_initial, uint64_t* out_off,
                uint64_t* location, int32_t* status, uint64_t* summary) {
-  if (multipart_required == 0) multipart_required = 1048576u;    // internal__size_multipart_required
   if (!ix || !sc->ready || !summary || first > sc->live || n > sc->live - first ||
       scratch_bytes < kdb_index_scan_scratch_bytes(n) ||
       (n && (!scratch || !keys_out || !key_off || !key_len || !stored_off || !avail || !svc || !size || !checksum ||
@@ -1675,22 +1592,15 @@ int scan_batch(const kdb_index* ix, const ScanState* sc, uint64_t nrows, void* s
     return KDB_PUT_EINVAL;
   if (sc->key_prefix[first + n] - sc->key_prefix[first] > keys_cap) return KDB_PUT_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(summary, 0, 5 * 8, st);
+  const hipError_t e = batch_begin(st, &multipart_required, summary);
   if (e != hipSuccess) return hip_code(e);
   if (n == 0) return KDB_PUT_OK;
   uint32_t* slot_len = reinterpret_cast<uint32_t*>(scratch);
-  const uint32_t waves = kGetBlock / 64;
-  const uint32_t g = std::min<uint32_t>((n + waves - 1u) / waves, 16384u);
-  hipLaunchKernelGGL(index_scan_emit_kernel, dim3(g), dim3(kGetBlock), 0, st, view_of(ix, nrows), sc->d_live,
-                     ix->d_rank_file, sc->d_key_prefix, first, n, multipart_required, keys_out, key_off, key_len,
-                     stored_off, avail, svc, size, checksum, checksum_initial, slot_len, location, status);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = launch_exclusive_scan(st, slot_len, n, out_off, summary + 1);
-  if (e != hipSuccess) return hip_code(e);
-  const uint32_t sg = std::min<uint32_t>((n + 255u) / 256u, 1024u);
-  hipLaunchKernelGGL(index_summary_kernel, dim3(sg), dim3(256), 0, st, avail, size, status, n,
-                     reinterpret_cast<unsigned long long*>(summary));
-  return hip_code(hipGetLastError());
+  hipLaunchKernelGGL(index_scan_emit_kernel, dim3(wave_grid(n)), dim3(kGetBlock), 0, st, view_of(ix, nrows),
+                     sc->d_live.get(), ix->a.d_rank_file.get(), sc->d_key_prefix.get(), first, n, multipart_required,
+                     keys_out, key_off, key_len, stored_off, avail, svc, size, checksum, checksum_initial, slot_len,
+                     location, status);
+  return batch_end(st, hipGetLastError(), slot_len, n, out_off, avail, size, status, summary);
 }
 
 }  // namespace
@@ -1771,7 +1681,6 @@ extern "C" int kdb_snapshot_scan_closed_live(const kdb_snapshot* snap, uint64_t*
 // Snapshot::Close (interface/snapshot.h:67-76)
 extern "C" int kdb_snapshot_release(kdb_snapshot* snap) {
   if (!snap) return KDB_PUT_EINVAL;
-  scan_release(&snap->scan);
   std::vector<kdb_snapshot*>& pins = snap->ix->pins;
   pins.erase(std::remove(pins.begin(), pins.end(), snap), pins.end());
   snap->ix->snapshots--;

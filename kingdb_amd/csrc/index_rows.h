@@ -8,7 +8,8 @@
 // The rows are read through a byte view: forwards for the offset array of a
 // closed file, backwards for the rows the device writer stages at the end of
 // its arena while a file is open (csrc/hstable_dev.hip: staged byte b lies at
-// arena[arena_bytes - 1 - b]).
+// arena[arena_bytes - 1 - b]).  The host's checks of an open file's record sit
+// here too: tail_range_ok and the order rule, sorts_after_loaded.
 #ifndef KDB_INDEX_ROWS_H_
 #define KDB_INDEX_ROWS_H_
 
@@ -56,6 +57,18 @@ KDB_HD bool tail_range_ok(uint64_t held_rows, uint64_t held_bytes, uint64_t rows
   const uint64_t nr = rows - held_rows, nb = row_bytes - held_bytes;
   if (nr > (1ull << 30) || nb < 2u * nr || nb > 15u * nr) return false;
   return row_bytes == 0 || rows_last >= row_bytes - 1u;
+}
+
+// The order rule of kdb_index_add_files and, ahead of time, of
+// kdb_index_set_tail: a fresh load of all the files numbers a new file's rows
+// after the loaded ones only if the file sorts after every loaded file by
+// (timestamp, fileid).  A file that did not load (status != 0) has no rows.
+KDB_HD bool sorts_after_loaded(const uint64_t* timestamps, const uint32_t* fileids, const int32_t* status,
+                               uint32_t nfiles, uint64_t timestamp, uint32_t fileid) {
+  for (uint32_t o = 0; o < nfiles; o++)
+    if (status[o] == 0 && (timestamp < timestamps[o] || (timestamp == timestamps[o] && fileid <= fileids[o])))
+      return false;
+  return true;
 }
 
 }  // namespace kdb_index_rows

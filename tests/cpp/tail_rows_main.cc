@@ -214,6 +214,22 @@ int main() {
     if (!ir::tail_range_ok(0, 0, 0, 0, 0) || !ir::tail_range_ok(3, 30, 3, 30, 100)) fail("nothing to parse");
     g_cases += 5;
   }
+  // the order rule: three loaded files of timestamp 5, 7, 7 and ids 4, 2, 9, and one that did not load
+  {
+    const uint64_t ts[4] = {5, 7, 9, 7};
+    const uint32_t id[4] = {4, 2, 100, 9};
+    const int32_t st[4] = {0, 0, -1, 0};
+    auto after = [&](uint32_t n, uint64_t t, uint32_t f) { return ir::sorts_after_loaded(ts, id, st, n, t, f); };
+    // the newest timestamp again: a smaller, an equal and a larger id
+    if (after(4, 7, 8) || after(4, 7, 9) || !after(4, 7, 10)) fail("equal timestamp");
+    if (after(4, 6, 1000) || after(4, 5, 5) || !after(4, 8, 0)) fail("older and newer timestamps");
+    // the file of timestamp 9 did not load: it is not in the way, with any id
+    if (!after(4, 8, 100) || !after(4, 9, 1)) fail("an unloaded file counts");
+    // only the files held: the first two, one, none
+    if (!after(2, 7, 3) || after(2, 7, 2) || !after(1, 5, 5) || after(1, 5, 4)) fail("files beyond the count");
+    if (!after(0, 0, 0) || !ir::sorts_after_loaded(nullptr, nullptr, nullptr, 0, 0, 0)) fail("an empty handle");
+    g_cases += 5;
+  }
   std::printf("ok %llu %llu\n", (unsigned long long)g_rows, (unsigned long long)g_cases);
   return 0;
 }

@@ -651,3 +651,144 @@ def test_no_tail_without_asking(gpu, runs):
     finally:
         ix.close()
         w.free()
+
+
+# ------------------------------------------------------------- 10. an add while a tail is held
+CLOSED = [(b"closed-%02d" % i, b"c" * (10 + i)) for i in range(25)]
+TAIL = [(b"tail-%02d" % i, b"t" * (40 + i)) for i in range(30)]
+OTHER = [(b"other-%02d" % i, b"o" * (5 + 2 * i)) for i in range(20)]
+ADDED = [(b"added-%02d" % i, b"a" * (70 + i)) for i in range(20)] + [(CLOSED[3][0], b"again")]
+
+
+@pytest.fixture(scope="module")
+def later(gpu):
+    """Files 1..4 of a writer fed CLOSED, TAIL, OTHER and ADDED with a close
+    after each (a file's timestamp is its id): file 1 and file 2 are, byte for
+    byte, what the writers of the tests below hold closed and open."""
+    batches = [CLOSED, TAIL, OTHER, ADDED]
+    w = new_writer(1 << 20, 1, batches, closes=4)
+    try:
+        for puts in batches:
+            feed(w, puts, 1)
+            w.close()
+        return w.files()
+    finally:
+        w.free()
+
+
+def tail_held(extra):
+    """(writer, index): CLOSED in the closed file 1, TAIL in the open file 2,
+    held as the tail; `extra` bytes of the arena beyond what the writer needs."""
+    from kingdb_amd import put
+    from kingdb_amd.index import HSTableIndex
+    w = put.DeviceHSTableWriter(1 << 20, 1, put.DeviceHSTableWriter.arena_bytes(
+        1 << 20, put.entries_bound(CLOSED) + put.entries_bound(TAIL), 55) + extra)
+    try:
+        ix = HSTableIndex.from_resident(w)
+        feed(w, CLOSED, 1)
+        w.close()
+        feed(w, TAIL, 1)
+        assert ix.refresh(tail=True) == 55 and ix.tail["rows"] == 30 and ix.tail_stats()[5] == buckets(55)
+        assert ix.get([TAIL[7][0], CLOSED[7][0]]) == [(0, TAIL[7][1]), (0, CLOSED[7][1])]
+        return w, ix
+    except BaseException:
+        w.free()
+        raise
+
+
+def place_in_arena(w, ix, files):
+    """Uploads `files` into the writer's arena, which the index borrows, between
+    the open file's end and the rows staged backwards from the arena's end (the
+    writer is not fed again): (file_off, file_size, fileid) for kdb_index_add_files."""
+    from kingdb_amd import _lib
+    rec = open_record(w)
+    at = (rec["file_off"] + rec["bytes"] + 4096 + 63) & ~63
+    off = []
+    for f in files:
+        off.append(at)
+        at = (at + len(files[f]) + 63) & ~63
+    assert at + 4096 <= rec["rows_last"] + 1 - rec["row_bytes"], "the arena has no room for the files"
+    for f, o in zip(files, off):
+        b = np.frombuffer(files[f], np.uint8)
+        _lib.check(_lib.load().kdb_lz4_memcpy_h2d(ix.files.ptr + o, b.ctypes.data, b.nbytes, None), "h2d")
+    _lib.check(_lib.load().kdb_lz4_stream_sync(None), "sync")
+    return (np.array(off, np.uint64), np.array([len(files[f]) for f in files], np.uint64),
+            np.array([int(f, 16) for f in files], np.uint32))
+
+
+def test_add_without_rows_drops_a_tail_with_rows(gpu, orc, later):
+    """One file with a broken footer CRC (-1) added while a tail of 30 rows is
+    held: no row comes in, and the tail's rows leave the buckets with it."""
+    from kingdb_amd.index import HSTableIndex, NOTFOUND
+    b = bytearray(later["00000003"])
+    b[M.footer(later["00000003"])[2] + 3] ^= 0x10            # a byte of the offset array: the footer's CRC is off
+    bad = {"00000003": bytes(b)}
+    assert M.Model(bad, orc, 1).file_status == {"00000003": -1}
+    q = queries([p[0] for p in CLOSED + TAIL + OTHER])
+    w, ix = tail_held(len(bad["00000003"]) + (64 << 10))
+    try:
+        off, size, fid = place_in_arena(w, ix, bad)
+        assert ix._add(None, off, size, fid) == {"00000003": -1}         # _add raises unless the call returns KDB_PUT_OK
+        assert ix.add_stats() == (0, buckets(25), 0)
+        assert ix.tail is None and ix.entries == 25
+        ix._sync_tail()                                       # the handle's own counts
+        assert ix.tail is None and ix.entries == 25
+        assert ix.tail_stats() == (0, 0, 0, 0, 30, buckets(25))          # [4]: the last set_tail's, as it was
+        assert ix.get([p[0] for p in TAIL]) == [(NOTFOUND, b"")] * 30
+        assert ix.get([p[0] for p in CLOSED]) == [(0, p[1]) for p in CLOSED]
+        fr = HSTableIndex({"00000001": later["00000001"]}, 1)
+        try:
+            assert snapshot(ix, q) == snapshot(fr, q)
+            assert list(ix.items()) == list(fr.items())
+        finally:
+            fr.close()
+        # the tail again: every row of it is parsed
+        assert ix.refresh(tail=True) == 30 and ix.tail_stats() == (1, 2, 30, w.open_bytes(), 30, buckets(55))
+        fr = HSTableIndex({f: later[f] for f in ("00000001", "00000002")}, 1)
+        try:
+            assert snapshot(ix, q) == snapshot(fr, q)
+            assert ix.get([p[0] for p in TAIL]) == [(0, p[1]) for p in TAIL]
+        finally:
+            fr.close()
+    finally:
+        ix.close()
+        w.free()
+
+
+def test_add_numbers_the_rows_again_with_a_tail_held(gpu, orc, later):
+    """Two files added in one call while a tail of 30 rows is held: the first
+    with a malformed offset array (-3, found by the parse, so the rows are
+    numbered a second time beside the tail's), the second good."""
+    from kingdb_amd.index import HSTableIndex
+    hashes = [0, 5, 127, 128, 300, 16383, 1 << 56, (1 << 63) - 1, 1 << 63, (1 << 64) - 1, 1 << 62, 7]
+    offsets = [5, 127, 128, 20000, 3000000, 0xFFFFFFF0, 0xFFFFFFFF, 0]
+    rows = [(hashes[(i * 7 + i // 12) % len(hashes)], offsets[(i * 3 + i // 8) % len(offsets)]) for i in range(90)]
+    g = M.with_rows(later["00000003"], rows, orc)
+    assert M.parse_rows(g) == rows
+    files = {"00000003": M.refooter(g, orc, num=len(rows) + 1),           # a row more than the array holds
+             "00000004": later["00000004"]}
+    want = {"00000001": later["00000001"], "00000004": later["00000004"]}
+    assert M.Model(dict(files, **want), orc, 1).file_status == {"00000001": 0, "00000003": -3, "00000004": 0}
+    q = queries([p[0] for p in CLOSED + TAIL + OTHER + ADDED])
+    w, ix = tail_held(sum(len(f) for f in files.values()) + (64 << 10))
+    try:
+        off, size, fid = place_in_arena(w, ix, files)
+        assert ix._add(None, off, size, fid) == {"00000003": -3, "00000004": 0}
+        good = len(ADDED)
+        # both passes count: the two files' rows, then the good file's alone
+        assert ix.add_stats() == (0, buckets(25 + good), (len(rows) + 1 + good) + good)
+        assert ix.tail is None and ix.entries == 25 + good
+        ix._sync_tail()
+        assert ix.tail is None and ix.entries == 25 + good and ix.tail_stats()[:4] == (0, 0, 0, 0)
+        fr = HSTableIndex(want, 1)
+        try:
+            snap = snapshot(ix, q)
+            assert snap == snapshot(fr, q)
+            assert_model(snap, M.Model(want, orc, 1), q)
+            assert list(ix.items()) == list(fr.items())
+        finally:
+            fr.close()
+        assert ix.get([ADDED[0][0], CLOSED[3][0], CLOSED[4][0]]) == [(0, ADDED[0][1]), (0, b"again"), (0, CLOSED[4][1])]
+    finally:
+        ix.close()
+        w.free()

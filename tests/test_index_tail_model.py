@@ -141,5 +141,6 @@ def test_row_decode_standalone_under_sanitizers(tmp_path):
     rows, cases = (int(x) for x in m.groups())
     # 600 rows of the length pairs, 69 of the edge counts, 5 000, and 301 splits of 300
     assert rows >= 600 + 69 + 5000 + 301 * 300
-    # 200 length pairs, 7 counts, 301 splits with 299 refused neighbours, 15 hostile and boundary cases
-    assert cases >= 200 + 7 + 301 + 299 + 15
+    # 200 length pairs, 7 counts, 301 splits with 299 refused neighbours, 15 hostile and boundary cases,
+    # 5 of the order rule (sorts_after_loaded)
+    assert cases >= 200 + 7 + 301 + 299 + 15 + 5
